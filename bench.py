@@ -22,9 +22,20 @@ Hessian -- prologue (two factorisations, replicated), k-means and the fused loop
 row losses / chosen rows -- and reports the per-phase seconds of rank 0 (`setup.rows_phases`).  Calibration is data-parallel
 there: every rank accumulates the Hessian of ITS share of the sequences and the partial sums meet in one all-reduce
 (`setup.hessian_s`, `setup.allreduce_s`).  With more than one GPU the default mode adds the same measurement as the
-`row_sharded` object, so one line carries both the weak- and the strong-scaling figure.
+`row_sharded` object, so one line carries both the weak- and the strong-scaling figure (with --full).
 
-Besides the driver contract the JSON line carries `roofline` (dominant kernel of the timed region, measured live
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of the last step when
+--dump-outputs DIR is given, and the result line (`metric`, `value`, `unit`, `ms_per_step`, `setup`, ...).
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # last step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                # every object below as well
+
+--dump-outputs writes, from rank 0, what the timed step hands its caller: `codebook` [m,V] float32, `dists` [K] float64,
+`best_k` [1] float64 and `indices_sample` (float32 rows of the [m,n] index matrix: all of them when they fit in 32 MiB,
+otherwise a fixed, seeded sample of rows, ascending).  The inputs are generated from fixed seeds, so two builds run with the
+same arguments can be compared output for output.
+
+With --full the JSON line also carries `roofline` (dominant kernel of the timed region, measured live
 with HIP events on the launch stream; `achieved` counts the flops of the rows the launches really solved -- converged
 rows are skipped from the third iteration on), `cpu_baseline` (oracle/ganq_oracle.c on this host's cores on a bounded
 sample of the same workload, the torch restatement of the reference's own op sequence beside it) and `lut_forward`
@@ -61,8 +72,9 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def build_workload(args, dist, dev):
-    """synthetic layer of SURVEY 8(d): W = 0.02*randn (fp16-rounded), X = randn * (0.1 + rand(n)) in 128 chunks"""
+def build_workload(args, dist, dev, warm_quantize=True):
+    """synthetic layer of SURVEY 8(d): W = 0.02*randn (fp16-rounded), X = randn * (0.1 + rand(n)) in 128 chunks.
+    warm_quantize: time a second complete quantize() on the same statistics (`setup.full_quantize_warm_s`)"""
     import torch.distributed as td
     import torch.nn as nn
 
@@ -139,18 +151,20 @@ def build_workload(args, dist, dev):
     wq, _, _, _, _, avg_loss, damp = q.quantize()  # full quantize(): prologue + k-means + loop + epilogue
     torch.cuda.synchronize()
     t_full = time.perf_counter() - t0
-    # the same call again on the same statistics: the first one pays one-time costs (workspaces, library handles)
-    q2 = GANQ(NamedModule(lin, "proj", f"model.layers.0.proj{seed_rank}", 0), qcfg)
-    q2.quantizer.configure(perchannel=True)
-    q2.H, q2.nsamples = H_copy, n_copy
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    q2.quantize()
-    torch.cuda.synchronize()
-    t_full_warm = time.perf_counter() - t0
+    t_full_warm = None
+    if warm_quantize:
+        # the same call again on the same statistics: the first one pays one-time costs (workspaces, library handles)
+        q2 = GANQ(NamedModule(lin, "proj", f"model.layers.0.proj{seed_rank}", 0), qcfg)
+        q2.quantizer.configure(perchannel=True)
+        q2.H, q2.nsamples = H_copy, n_copy
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        q2.quantize()
+        torch.cuda.synchronize()
+        t_full_warm = round(time.perf_counter() - t0, 4)
     captured.update(lin=lin, qcfg=qcfg, H_raw=H_copy, nsamples=n_copy)
     setup = {"hessian_s": round(t_hess, 4), "xgmi_broadcast_s": round(t_bcast, 4), "allreduce_s": round(t_allreduce, 4), "kmeans_s": round(captured["kmeans_s"], 4),
-             "full_quantize_s": round(t_full, 4), "full_quantize_warm_s": round(t_full_warm, 4), "avg_loss": avg_loss, "damp_percent": damp,
+             "full_quantize_s": round(t_full, 4), "full_quantize_warm_s": t_full_warm, "avg_loss": avg_loss, "damp_percent": damp,
              "calib_bytes": args.nseq * args.seqlen * n * 2}
     return captured, setup
 
@@ -497,6 +511,86 @@ def executed_rows(cap, args):
     return rows[:args.iters]
 
 
+DUMP_INDEX_BYTES = 32 << 20  # float32 rows of the index matrix written by --dump-outputs (the whole dump stays under 64 MB)
+
+
+def dump_outputs(out, dirpath):
+    """the arrays the timed step returns to its caller, as DIR/<name>.npy in float32 / float64: codebook, dists, best_k and
+    the index matrix (a fixed, seeded sample of its rows when all of them would exceed DUMP_INDEX_BYTES)"""
+    import numpy as np
+
+    T, Q, dists, best_k = out
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {"dists": dists.double().cpu().numpy(), "best_k": np.array([int(best_k)], dtype=np.float64)}
+    if T is not None:
+        arrays["codebook"] = T.float().cpu().numpy()
+    if Q is not None:
+        m, n = Q.shape
+        keep = max(1, DUMP_INDEX_BYTES // (4 * n))
+        rows = torch.arange(m) if keep >= m else torch.from_numpy(np.sort(np.random.default_rng(0).choice(m, keep, replace=False)))
+        arrays["indices_sample"] = Q[rows.to(Q.device)].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    log(f"[bench] outputs of the last step -> {dirpath}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
+
+
+def roofline_report(prof_all, prof, dom_name, exec_rows, exec_frac, elapsed, args, dist):
+    """`roofline`, `path_hbm` and `kernels` of the full line: the dominant kernel of the timed region from its HIP events,
+    the whole-path algorithmic bytes over the loop time, and the per-kernel table of the instrumented step"""
+    m, n, K, V = args.m, args.n, args.iters, 2 ** args.bits
+    kern = {k: {"total_ms": round(v[0], 3), "launches": v[1], "avg_ms": round(v[0] / v[1], 4)} for k, v in prof_all.items()}
+    dom_ms, dom_cnt = prof[dom_name]  # HIP events over the timed region, on the stream the kernel is launched on
+    avg_s = dom_ms / dom_cnt / 1e3
+    if dom_name == "solve_s_kernel":
+        # residual chain: n(n-1)/2 fused multiply-adds per SOLVED row on the fp32 matrix cores; converged rows are
+        # skipped from the third iteration on, so the flops are those of the rows the launches really solved
+        m_loc = m if args.mode == "layers" else (m + dist.world - 1) // dist.world
+        work_full = float(m_loc) * n * (n - 1)
+        work = work_full * exec_frac
+        roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
+                "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "peak_dtype": "f32",
+                "executed_rows_per_iteration": exec_rows, "executed_fraction_of_reference_flops": round(exec_frac, 4),
+                "achieved_if_all_rows_counted": round(work_full / avg_s / 1e12, 3)}
+    elif dom_name == "onehot_accum_kernel":
+        # bucket sum of H per row on the int8 matrix cores: one-hot [16 codes] x 4 digit planes, pairs u > v only
+        work = 2.0 * 16 * 4 * m * n * (n - 1) / 2
+        roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
+                "peak": INT8_MFMA_PEAK_TOPS, "unit": "TFLOP/s", "peak_dtype": "i8 (dense, 2x bf16)"}
+    elif dom_name == "gemm_f32_kernel":
+        work = 2.0 * m * n * n
+        roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
+                "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "peak_dtype": "f32"}
+    else:
+        nbytes = 4.0 * n * n + 1.0 * m * n
+        roof = {"kernel": dom_name, "bound": "hbm", "achieved": round(nbytes / avg_s / 1e9, 2), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s"}
+    roof["frac"] = round(roof["achieved"] / roof["peak"], 5)
+    roof["avg_launch_ms"] = round(dom_ms / dom_cnt, 4)
+    # HBM bytes per launch from the PMC counters of a separate rocprofv3 --pmc pass over the same kernels
+    # (profiles/<PMC_FILE>, tools/pmc_collect.sh; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950)
+    roof["traffic"] = None
+    try:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from pmc_parse import csrc_digest
+
+        pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+        if pmc.get("_csrc_sha256") != csrc_digest(ROOT):
+            roof["traffic_note"] = f"profiles/{PMC_FILE} was collected on other kernel sources than the ones running: not reported"
+        else:
+            for k, v in pmc.items():
+                if k.split("<")[0] == dom_name and (m, n) == (4096, 4096):
+                    roof["traffic"] = int((2.0 * v["FETCH_SIZE_KB_avg"] + v["WRITE_SIZE_KB_avg"]) * 1024)
+                    roof["traffic_source"] = f"profiles/{PMC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH_SIZE x2 for gfx950)"
+    except (OSError, ValueError, KeyError, AttributeError):
+        pass
+    # whole-path HBM view (SURVEY 8d): algorithmic bytes of the loop per layer / loop time
+    b_loop = K * (15.0 * m * n + 10.0 * n * n + 8.0 * m * V)
+    path_gbs = b_loop / (elapsed / args.steps) / 1e9
+    path_hbm = {"algorithmic_GB_per_layer": round(b_loop / 1e9, 3), "achieved_GBs": round(path_gbs, 2),
+                "frac_of_peak": round(path_gbs / HBM_PEAK_GBS, 5)}
+    return roof, path_hbm, kern
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -508,19 +602,26 @@ def main():
     ap.add_argument("--iters", type=int, default=10, help="GANQ iterations K (README PPL numbers use 10)")
     ap.add_argument("--nseq", type=int, default=128)
     ap.add_argument("--seqlen", type=int, default=2048)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel table and roofline, row-sharded quantize(), "
+                         "CPU baseline, LUT forward, whole-model runs, 3-bit stress, PPL objects")
     ap.add_argument("--cpu-rows", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lut", action="store_true", help="skip the lut_forward object")
-    ap.add_argument("--no-opt125m", action="store_true", help="skip the opt125m object (whole-model run on the opt-125m architecture)")
-    ap.add_argument("--no-llama", action="store_true", help="skip the llama32_1b object (whole-model run on the Llama-3.2-1B architecture)")
-    ap.add_argument("--no-stress", action="store_true", help="skip the stress_3bit object (V = 8, 512 calibration sequences)")
-    ap.add_argument("--no-tiny", action="store_true", help="skip the ppl_tiny object (trained tiny model, PPL vs the reference's GANQ)")
-    ap.add_argument("--model-path", default=None, help="local HF model directory: adds measured Wiki2 PPL (fp16 / GANQ) to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
+    ap.add_argument("--no-lut", action="store_true", help="with --full: skip the lut_forward object")
+    ap.add_argument("--no-opt125m", action="store_true", help="with --full: skip the opt125m object (whole-model run on the opt-125m architecture)")
+    ap.add_argument("--no-llama", action="store_true", help="with --full: skip the llama32_1b object (whole-model run on the Llama-3.2-1B architecture)")
+    ap.add_argument("--no-stress", action="store_true", help="with --full: skip the stress_3bit object (V = 8, 512 calibration sequences)")
+    ap.add_argument("--no-tiny", action="store_true", help="with --full: skip the ppl_tiny object (trained tiny model, PPL vs the reference's GANQ)")
+    ap.add_argument("--model-path", default=None, help="with --full: local HF model directory: adds measured Wiki2 PPL (fp16 / GANQ) to the line")
     ap.add_argument("--wikitext-path", default=None)
     ap.add_argument("--c4-path", default=None)
     ap.add_argument("--mode", choices=["layers", "rows"], default="layers",
                     help="layers: one layer per GPU (weak scaling, the default); rows: one layer, rows split over the GPUs (strong)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from ganq_amd import _lib
     from ganq_amd import distributed as gdist
@@ -535,9 +636,9 @@ def main():
     import torch.distributed as td
 
     if args.mode == "rows":
-        cap, setup = build_workload(args, _SameSeed(dist), dev)  # every rank needs the SAME layer
+        cap, setup = build_workload(args, _SameSeed(dist), dev, warm_quantize=args.full)  # every rank needs the SAME layer
     else:
-        cap, setup = build_workload(args, dist, dev)
+        cap, setup = build_workload(args, dist, dev, warm_quantize=args.full)
     V = 2 ** args.bits
     ws = _lib.run_layer_workspace(args.m, args.n, V, dev)
 
@@ -546,7 +647,7 @@ def main():
 
         def step():
             q = sharded_step()
-            return None, None, q.ganq_stats["dists"], q.ganq_stats["best_k"]
+            return q.ganq_codebook, q.ganq_indices, q.ganq_stats["dists"], q.ganq_stats["best_k"]
     else:
         def step():
             return _lib.run_layer(cap["W"], cap["H"], cap["L"], cap["T0"], args.iters, alias_q=True, workspace=ws)
@@ -555,20 +656,23 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # per-kernel breakdown: ONE extra untimed step with every kernel instrumented.  The events of a fully instrumented
-    # run sit between dependent launches and cost about 1 ms of idle time per layer, so the timed steps below carry
-    # events only around the dominant kernel (the one the roofline object is about).
-    _lib.profile_enable(True)
-    step()
-    prof_all = _lib.profile_report()
-    _lib.profile_enable(False)
-    dom_name = max(prof_all.items(), key=lambda kv: kv[1][0])[0]
-    if args.mode == "rows" and "solve_s_kernel" in prof_all:
-        dom_name = "solve_s_kernel"  # the roofline object stays on the loop's dominant kernel (k-means is outside t_loop)
+    prof_all = dom_name = None
+    if args.full:
+        # per-kernel breakdown: ONE extra untimed step with every kernel instrumented.  The events of a fully instrumented
+        # run sit between dependent launches and cost about 1 ms of idle time per layer, so the timed steps below carry
+        # events only around the dominant kernel (the one the roofline object is about).
+        _lib.profile_enable(True)
+        step()
+        prof_all = _lib.profile_report()
+        _lib.profile_enable(False)
+        dom_name = max(prof_all.items(), key=lambda kv: kv[1][0])[0]
+        if args.mode == "rows" and "solve_s_kernel" in prof_all:
+            dom_name = "solve_s_kernel"  # the roofline object stays on the loop's dominant kernel (k-means is outside t_loop)
     torch.cuda.synchronize()
     if dist.world > 1:
         td.barrier()
-    _lib.profile_enable(True, only=dom_name)
+    if args.full:
+        _lib.profile_enable(True, only=dom_name)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -578,21 +682,25 @@ def main():
         td.barrier()
     elapsed = time.perf_counter() - t0
     log(f"[bench] timed region: {args.steps} steps in {elapsed:.4f} s")
-    prof = _lib.profile_report()
-    _lib.profile_enable(False)
+    prof = None
+    if args.full:
+        prof = _lib.profile_report()
+        _lib.profile_enable(False)
     if dist.world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
         if td.get_backend() != "gloo":
             t = t.to(dev)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # strong-scaling figure: the SAME layer (rank 0's) quantized by all ranks together -- data-parallel statistics are
     # already reduced in rows mode; in layers mode rank 0's weight and Hessian are broadcast first
     row_sharded = phases = None
-    if args.mode == "rows":
+    if args.full and args.mode == "rows":
         phases = rows_phases(cap, dist)
-    else:  # every N (also 1): the complete row-sharded quantize() of rank 0's layer, with its phases
+    elif args.full:  # every N (also 1): the complete row-sharded quantize() of rank 0's layer, with its phases
         if dist.world > 1:
             gdist.broadcast_tensor(cap["lin"].weight.data, 0)
             gdist.broadcast_tensor(cap["H_raw"], 0)
@@ -617,60 +725,12 @@ def main():
                        "single_gpu_full_quantize_warm_ms": round(setup["full_quantize_warm_s"] * 1e3, 3), "phases_rank0_s": phases}
 
     exec_rows, exec_frac = None, 1.0
-    if dist.rank == 0 and args.mode == "layers":
+    if args.full and dist.rank == 0 and args.mode == "layers":
         exec_rows = executed_rows(cap, args)
         exec_frac = sum(exec_rows) / float(args.m * args.iters)
     if dist.rank == 0:
         m, n, K = args.m, args.n, args.iters
         value = (dist.world if args.mode == "layers" else 1) * args.steps * n / elapsed
-        kern = {k: {"total_ms": round(v[0], 3), "launches": v[1], "avg_ms": round(v[0] / v[1], 4)} for k, v in prof_all.items()}
-        dom_ms, dom_cnt = prof[dom_name]  # HIP events over the timed region, on the stream the kernel is launched on
-        avg_s = dom_ms / dom_cnt / 1e3
-        if dom_name == "solve_s_kernel":
-            # residual chain: n(n-1)/2 fused multiply-adds per SOLVED row on the fp32 matrix cores; converged rows are
-            # skipped from the third iteration on, so the flops are those of the rows the launches really solved
-            m_loc = m if args.mode == "layers" else (m + dist.world - 1) // dist.world
-            work_full = float(m_loc) * n * (n - 1)
-            work = work_full * exec_frac
-            roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
-                    "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "peak_dtype": "f32",
-                    "executed_rows_per_iteration": exec_rows, "executed_fraction_of_reference_flops": round(exec_frac, 4),
-                    "achieved_if_all_rows_counted": round(work_full / avg_s / 1e12, 3)}
-        elif dom_name == "onehot_accum_kernel":
-            # bucket sum of H per row on the int8 matrix cores: one-hot [16 codes] x 4 digit planes, pairs u > v only
-            work = 2.0 * 16 * 4 * m * n * (n - 1) / 2
-            roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
-                    "peak": INT8_MFMA_PEAK_TOPS, "unit": "TFLOP/s", "peak_dtype": "i8 (dense, 2x bf16)"}
-        elif dom_name == "gemm_f32_kernel":
-            work = 2.0 * m * n * n
-            roof = {"kernel": dom_name, "bound": "mfma", "achieved": round(work / avg_s / 1e12, 3),
-                    "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "peak_dtype": "f32"}
-        else:
-            nbytes = 4.0 * n * n + 1.0 * m * n
-            roof = {"kernel": dom_name, "bound": "hbm", "achieved": round(nbytes / avg_s / 1e9, 2), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s"}
-        roof["frac"] = round(roof["achieved"] / roof["peak"], 5)
-        roof["avg_launch_ms"] = round(dom_ms / dom_cnt, 4)
-        # HBM bytes per launch from the PMC counters of a separate rocprofv3 --pmc pass over the same kernels
-        # (profiles/<PMC_FILE>, tools/pmc_collect.sh; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950)
-        roof["traffic"] = None
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from pmc_parse import csrc_digest
-
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
-            if pmc.get("_csrc_sha256") != csrc_digest(ROOT):
-                roof["traffic_note"] = f"profiles/{PMC_FILE} was collected on other kernel sources than the ones running: not reported"
-            else:
-                for k, v in pmc.items():
-                    if k.split("<")[0] == dom_name and (m, n) == (4096, 4096):
-                        roof["traffic"] = int((2.0 * v["FETCH_SIZE_KB_avg"] + v["WRITE_SIZE_KB_avg"]) * 1024)
-                        roof["traffic_source"] = f"profiles/{PMC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH_SIZE x2 for gfx950)"
-        except (OSError, ValueError, KeyError, AttributeError):
-            pass
-        # whole-path HBM view: algorithmic bytes of the loop per layer / loop time
-        b_loop = K * (15.0 * m * n + 10.0 * n * n + 8.0 * m * V)
-        path_gbs = b_loop / (elapsed / args.steps) / 1e9
         result = {
             "metric": "weight-columns quantized/sec @4096x4096 (GANQ 4-bit, K=10 alternating-optimisation loop)",
             "value": round(value, 2), "unit": "columns/s", "n_gpus": dist.world, "steps": args.steps,
@@ -682,47 +742,49 @@ def main():
                        "m": m, "n": n, "bits": args.bits, "ganq_iterations": K, "mode": args.mode,
                        "parallelism": f"layers x{dist.world}" if args.mode == "layers" else f"rows /{dist.world}"},
             "column_steps_per_s": round(value * K, 1),
-            "roofline": roof,
-            "path_hbm": {"algorithmic_GB_per_layer": round(b_loop / 1e9, 3), "achieved_GBs": round(path_gbs, 2),
-                         "frac_of_peak": round(path_gbs / HBM_PEAK_GBS, 5)},
-            "kernels": kern,
-            "kernels_note": "one extra untimed step with every kernel instrumented; the timed steps carry HIP events around "
-                            f"{dom_name} only (events between dependent launches cost idle time)",
+        }
+        if args.full:
+            roof, path_hbm, kern = roofline_report(prof_all, prof, dom_name, exec_rows, exec_frac, elapsed, args, dist)
+            result.update({
+                "roofline": roof, "path_hbm": path_hbm, "kernels": kern,
+                "kernels_note": "one extra untimed step with every kernel instrumented; the timed steps carry HIP events around "
+                                f"{dom_name} only (events between dependent launches cost idle time)"})
+        result.update({
             "setup": setup,
             "dists_last_step": [round(float(x), 6) for x in out[2].cpu().tolist()], "best_k": int(out[3]),
             "parity": "this exact workload, K = 10, is checked against the CPU oracle by tests/test_hip_configs.py::"
                       "test_bench_workload_k10_vs_oracle (indices bit-exact, codebooks <= 1e-5, row losses <= 1e-6)",
-        }
+        })
         if phases is not None and args.mode == "rows":
             result["setup"]["rows_phases"] = phases
         if row_sharded is not None:
             result["row_sharded"] = row_sharded
-        if dist.world == 1 and not args.no_cpu_baseline:
+        if args.full and dist.world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(cap, args)
             result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)
-        if dist.world == 1 and not args.no_lut:
+        if args.full and dist.world == 1 and not args.no_lut:
             cap = ws = None  # free the layer before the rings of weights are allocated
             torch.cuda.empty_cache()
             log("[bench] lut_forward ...")
             result["lut_forward"] = lut_forward_report()
-        if dist.world == 1 and not args.no_opt125m:
+        if args.full and dist.world == 1 and not args.no_opt125m:
             log("[bench] opt125m (whole-model run on the architecture + C oracle loops) ...")
             cap = ws = None
             torch.cuda.empty_cache()
             result["opt125m"] = opt125m_report(args)
-        if dist.world == 1 and not args.no_llama:
+        if args.full and dist.world == 1 and not args.no_llama:
             log("[bench] llama32_1b (whole-model run on the architecture) ...")
             torch.cuda.empty_cache()
             result["llama32_1b"] = llama32_1b_report(args)
-        if dist.world == 1 and not args.no_stress:
+        if args.full and dist.world == 1 and not args.no_stress:
             log("[bench] stress_3bit (V = 8, 512 sequences) ...")
             torch.cuda.empty_cache()
             result["stress_3bit"] = stress_3bit_report(args, dist, dev)
-        if dist.world == 1 and not args.no_tiny:
+        if args.full and dist.world == 1 and not args.no_tiny:
             log("[bench] ppl_tiny (trained tiny model vs the reference's GANQ) ...")
             torch.cuda.empty_cache()
             result["ppl_tiny"] = ppl_tiny_report()
-        if dist.world == 1:
+        if args.full and dist.world == 1:
             result["ppl"] = ppl_report(args)
         print(json.dumps(result), flush=True)
     if dist.world > 1:

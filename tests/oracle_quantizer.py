@@ -11,7 +11,10 @@ oracle and the reference's own op sequence:
   outputs      ganq.py:633-646, gptq.py:324-375
 `OracleProcessor` is the product's GPTQProcessor with this quantizer in the GANQ slot.  Nothing under ganq_amd/ imports
 this file.
+The torch CPU ops run on ONE thread (`host_threads`): LAPACK's factorisations round differently with the thread count, and
+the oracle's bits must not depend on how many cores the host grants the process.
 """
+import contextlib
 import copy
 import time
 
@@ -21,6 +24,20 @@ import torch
 from ganq_amd.looper.gptq_processor import GPTQProcessor
 from ganq_amd.quantization.quantizer import Quantizer
 from oracle import c_oracle
+
+
+ORACLE_TORCH_THREADS = 1
+
+
+@contextlib.contextmanager
+def host_threads(n=ORACLE_TORCH_THREADS):
+    """torch CPU ops inside the block run on n threads (the caller's setting is restored afterwards)"""
+    before = torch.get_num_threads()
+    torch.set_num_threads(n)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(before)
 
 
 class OracleSolver:
@@ -72,7 +89,8 @@ class OracleGANQ:
         self.H *= self.nsamples / (self.nsamples + batch)
         self.nsamples += batch
         x = (2.0 / self.nsamples) ** 0.5 * x.float()
-        self.H += x.matmul(x.t())
+        with host_threads():
+            self.H += x.matmul(x.t())
 
     def _prologue_key(self):
         return id(self)  # never shares a prologue
@@ -86,31 +104,32 @@ class OracleGANQ:
         c = self.qcfg
         W, H = self.W, self.H
         self.quantizer.find_params(W, weight=True)
-        dead = torch.diag(H) == 0
-        H[dead, dead] = 1
-        if c.dead == "zero":
-            W[:, dead] = 0
-        else:
-            W[:, dead] = torch.mean(W[:, ~dead], dim=1, keepdim=True)
-        perm = invperm = None
-        if c.act_sort != "none":
-            perm = torch.argsort(torch.diag(H), descending=c.act_sort == "desc")
-            W = W[:, perm].contiguous()
-            H = H[perm][:, perm].contiguous()
-            invperm = torch.argsort(perm)
-        L = None
-        if c.l_damp_style == "ganq":
-            offset = (torch.sum(torch.abs(H), dim=1) - 2 * torch.diag(H)).clamp(min=1e-8)
-            L = torch.linalg.cholesky(H + torch.diag(offset))
-        damp_percent = c.damp_percent
-        damp = damp_percent * torch.mean(torch.diag(H))
-        diag = torch.arange(self.columns)
-        H[diag, diag] += damp
-        Xxt_damped = H.clone()
-        Lg = torch.linalg.cholesky(H)
-        if c.l_damp_style == "gptq":
-            L = Lg.clone()
-        Hinv = torch.linalg.cholesky(torch.cholesky_inverse(Lg), upper=True)
+        with host_threads():
+            dead = torch.diag(H) == 0
+            H[dead, dead] = 1
+            if c.dead == "zero":
+                W[:, dead] = 0
+            else:
+                W[:, dead] = torch.mean(W[:, ~dead], dim=1, keepdim=True)
+            perm = invperm = None
+            if c.act_sort != "none":
+                perm = torch.argsort(torch.diag(H), descending=c.act_sort == "desc")
+                W = W[:, perm].contiguous()
+                H = H[perm][:, perm].contiguous()
+                invperm = torch.argsort(perm)
+            L = None
+            if c.l_damp_style == "ganq":
+                offset = (torch.sum(torch.abs(H), dim=1) - 2 * torch.diag(H)).clamp(min=1e-8)
+                L = torch.linalg.cholesky(H + torch.diag(offset))
+            damp_percent = c.damp_percent
+            damp = damp_percent * torch.mean(torch.diag(H))
+            diag = torch.arange(self.columns)
+            H[diag, diag] += damp
+            Xxt_damped = H.clone()
+            Lg = torch.linalg.cholesky(H)
+            if c.l_damp_style == "gptq":
+                L = Lg.clone()
+            Hinv = torch.linalg.cholesky(torch.cholesky_inverse(Lg), upper=True)
         hd = torch.diagonal(Hinv)
         V = 2 ** c.bits
         weights = (hd ** (-4)).double().numpy()

@@ -138,7 +138,9 @@ def test_opt125m_architecture_hip_vs_cpu_oracle_at_model_boundary():
     with the example's settings (basic_usage_wikitext2.py:126-141), quantized twice through the same looper: once by the
     HIP path, once by the CPU oracle in the quantizer slot (tests/oracle_quantizer.py: the reference's op sequence on
     the host).  The two quantized models must agree in their logits and in the GPTQ-style perplexity to the metric's
-    tolerance: +-0.05 at the reference's 28.45, i.e. 0.18 % relative."""
+    tolerance: +-0.05 at the reference's 28.45, i.e. 0.18 % relative.  The perplexity is taken over 32 windows of 512
+    random tokens: on 4 windows the sample alone moves it by more than that (fp16 model 57630 on 4 windows, 57372 on 8,
+    58447 on 32), while the gap between the two quantized models measured 0.19 % on 4, 0.07 % on 8, 0.02 % on 32."""
     import copy
 
     import transformers
@@ -153,7 +155,7 @@ def test_opt125m_architecture_hip_vs_cpu_oracle_at_model_boundary():
     base = transformers.OPTForCausalLM(cfg).half().cuda().eval()
     g = torch.Generator().manual_seed(1)
     calib = [torch.randint(0, cfg.vocab_size, (2, 256), generator=g) for _ in range(4)]
-    test_ids = torch.randint(0, cfg.vocab_size, (1, 4 * 512), generator=g)
+    test_ids = torch.randint(0, cfg.vocab_size, (1, 32 * 512), generator=g)
 
     def qcfg():
         return QuantizeConfig(bits=4, quant_method="ganq", format="fake", act_sort="asc", l_damp_style="ganq", dead="mean",

@@ -7,8 +7,8 @@ T=${1:-rXX}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-echo "[collect] bench"; python3 bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err || tail -3 $O/${T}_bench.err
-echo "[collect] kernel stats"; bash tools/bench_stats.sh 30 > $O/${T}_bench_stats.txt 2>&1; cp $O/bench_kernel_stats.csv $O/${T}_bench_kernel_stats.csv
+echo "[collect] bench"; python3 bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err || tail -3 $O/${T}_bench.err
+echo "[collect] kernel stats"; OUT_DIR=$O bash tools/bench_stats.sh 30 > $O/${T}_bench_stats.txt 2>&1; cp $O/bench_kernel_stats.csv $O/${T}_bench_kernel_stats.csv
 echo "[collect] pmc traffic"; bash tools/pmc_collect.sh $O/${T}_pmc_traffic.json > $O/${T}_pmc.txt 2>&1
 echo "[collect] models"; python3 tools/quantize_model_bench.py --arch llama-3.2-1b > $O/${T}_model_llama32_1b.json 2> $O/${T}_model.err
 python3 tools/quantize_model_bench.py --arch opt-125m > $O/${T}_model_opt125m.json 2>> $O/${T}_model.err

@@ -37,6 +37,7 @@ SIGNATURES = {
     "ganq_hessian_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "ganq_hessian_accum": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_sz, _c_vp]),
     "ganq_debug_hessian_t_cut": (ctypes.c_int, [_c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, ctypes.c_int, _c_vp, ctypes.c_int]),
+    "ganq_debug_hessian_t_check": (ctypes.c_int, [_c_i64, _c_i64, ctypes.c_int]),
     "ganq_hessian_t_supported": (ctypes.c_int, [_c_i64, _c_i64]),
     "ganq_hessian_t_workspace_bytes": (_c_sz, [_c_i64]),
     "ganq_hessian_stage_t": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
@@ -419,9 +420,19 @@ def debug_gemm_h16(x, w, bias=None, addend=None):
     return y
 
 
-def hessian_accum(H, X, nsamples_before: int, batch: int):
+def _caller_workspace(ws, nbytes: int, what: str):
+    """a workspace the caller passed (tests fill it with a pattern): contiguous, on the GPU, at least `nbytes` -> (ws, its bytes)"""
+    if not (ws.is_cuda and ws.is_contiguous()):
+        raise GanqHipError(f"{what}: the workspace must be a contiguous cuda tensor")
+    have = ws.numel() * ws.element_size()
+    if have < nbytes:
+        raise GanqHipError(f"{what}: workspace of {have} B < the {nbytes} B required")
+    return ws, have
+
+
+def hessian_accum(H, X, nsamples_before: int, batch: int, workspace=None):
     """gptq.py:96-131.  H [n,n] fp32 (updated in place), X [rows, n] fp16/bf16 (one calibration batch of
-    `batch` sequences, flattened)."""
+    `batch` sequences, flattened).  workspace: optional caller-owned scratch of at least ganq_hessian_workspace_bytes."""
     if not (H.is_cuda and H.dtype == torch.float32 and H.is_contiguous()):
         raise GanqHipError("H must be a contiguous float32 cuda tensor")
     code = _act_dtype(X, "X")
@@ -433,7 +444,10 @@ def hessian_accum(H, X, nsamples_before: int, batch: int):
     # re-uses it from call to call; nothing outlives the call on the library's side)
     with torch.cuda.device(H.device):
         nbytes = lib().ganq_hessian_workspace_bytes(rows, n)
-    ws = _workspace(nbytes, H.device) if nbytes else None
+    if workspace is not None:
+        ws, nbytes = _caller_workspace(workspace, nbytes, "hessian_accum")
+    else:
+        ws = _workspace(nbytes, H.device) if nbytes else None
     _call("ganq_hessian_accum", (H, X, ws), H.data_ptr(), X.data_ptr(), code, rows, n, int(nsamples_before), int(batch),
           ws.data_ptr() if ws is not None else None, int(nbytes), _ST)
     return H
@@ -458,9 +472,9 @@ def hessian_stage_t(Xt, X, tok0: int):
     return Xt
 
 
-def hessian_accum_t(H, Xt, rows: int, nsamples_before: int, batch: int):
+def hessian_accum_t(H, Xt, rows: int, nsamples_before: int, batch: int, workspace=None):
     """gptq.py:96-131 for a staged group in transposed layout: H [n,n] fp32 (in place), Xt [n, ldt], its first `rows` tokens
-    (a multiple of 32) = `batch` sequences"""
+    (a multiple of 32) = `batch` sequences.  workspace: optional caller-owned scratch of at least ganq_hessian_t_workspace_bytes."""
     if not (H.is_cuda and H.dtype == torch.float32 and H.is_contiguous()):
         raise GanqHipError("H must be a contiguous float32 cuda tensor")
     code = _act_dtype(Xt, "Xt")
@@ -469,7 +483,10 @@ def hessian_accum_t(H, Xt, rows: int, nsamples_before: int, batch: int):
     n, ldt = Xt.shape
     with torch.cuda.device(H.device):
         nbytes = lib().ganq_hessian_t_workspace_bytes(n)
-    ws = _workspace(nbytes, H.device)
+    if workspace is not None:
+        ws, nbytes = _caller_workspace(workspace, nbytes, "hessian_accum_t")
+    else:
+        ws = _workspace(nbytes, H.device)
     _call("ganq_hessian_accum_t", (H, Xt, ws), H.data_ptr(), Xt.data_ptr(), ldt, code, int(rows), n, int(nsamples_before), int(batch),
           ws.data_ptr(), int(nbytes), _ST)
     return H

@@ -81,6 +81,7 @@ enum Opt : int {
     OPT_LUT_DENSE_M,
     OPT_HESS_W4,
     OPT_KMEANS_SPAN,
+    OPT_HESS_W4_WGS,
     OPT_COUNT
 };
 long long opt_get(int id);

@@ -8,14 +8,17 @@
 //     needs 32 of them per slice.  So the batch is transposed ONCE (hw_transpose_kernel: Xt [feature][token] in the workspace, the
 //     transposed reads used there, where they cost nothing against the memory traffic) and the main kernel is the dense GEMM's
 //     Xt Xt^T: 64-byte rows in LDS, slot XOR (row >> 2) & 3, plain 16-byte fragment reads;
-//   * only tiles on or below the diagonal exist (136 at n = 4096, fewer than CUs), so the launch is cut STREAM-K: the (tile, slice)
-//     pairs are one linear range, every workgroup (one per CU) takes an equal contiguous share of it -- at most two partial tiles
-//     and any number of whole ones.  A partial tile is stored in register order, write-through (sc1), the workgroup takes a ticket on
-//     the tile's counter and the LAST one to arrive sums the parts IN RANGE ORDER (its own from registers at its place in the order):
-//     no atomics on data, no waiting, the same bits whoever finishes.  The mirror image is written from the same registers.
+//   * only tiles on or below the diagonal exist (136 at n = 4096, fewer than CUs), so the launch is cut STREAM-K over G workgroups
+//     (one per CU; see "the cut of a launch" below): every workgroup first takes T div G whole tiles, then a share of the T mod G
+//     tiles left over -- a primary's head of a tile, or a helper's range of tails that touches at most three tiles.  A whole tile,
+//     and a left-over tile that the cut leaves in one part, is finished from the registers, its mirror image from the same registers.
+//     Every other part is stored in register order into one of the workgroup's W_SLOTS partial tiles, and hessian_w4_fix_kernel, a
+//     second launch, sums the parts of each tile of two or more parts in the order of the cut and writes the tile and its mirror:
+//     no atomics, no waiting, the same bits from run to run.
 // fp16 x fp16 products are exact in fp32, so this differs from the other Hessian kernels only in the grouping of the fp32 sums.
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "mfma_h16.h"
@@ -31,7 +34,7 @@ constexpr int W_ST = 2 * W_IMG;         // a stage: u image + v image
 constexpr int W_NST = 4;
 constexpr int W_PART = WT * WT;         // floats of a partial tile
 constexpr int W_SLOTS = 3;             // partial tiles a workgroup may leave (a helper range touches at most three tiles)
-constexpr int W_MAX_TILES = 4096;       // (n <= 23 k; the head of the workspace is reserved for as many words)
+constexpr int W_MAX_TILES = 4096;       // (n <= 23 k; the head of the workspace is reserved for as many words, the partial tiles follow)
 
 typedef short hw_s4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef uint32_t hw_u32x2 __attribute__((ext_vector_type(2)));
@@ -84,15 +87,17 @@ __global__ __launch_bounds__(256) void hw_stage_kernel(const uint16_t* __restric
         }
 }
 
-// ---- the cut of a launch (shared by the host, the kernels and the CPU test of the cut: tests/test_host_logic.py through
-// ganq_debug_hessian_t_cut).  T tiles of Ks token slices on G workgroups: W = T div G whole tiles per workgroup first (tile w G + c:
-// everybody walks the tokens of a row of tiles in step, the operand panels are shared in the L2).  The R = T mod G tiles left over are
-// cut so that the workgroups still read the same tokens at the same time: workgroup c < nprim is the PRIMARY of left-over tile c and
-// takes its slices [0, P); the others are HELPERS that share the tails [P, Ks) of all left-over tiles in equal contiguous ranges of Sh
-// slices, each started at the tile boundary inside its range (primaries are at slice tau, helpers at P + tau or P + tau - (Sh - Lt) at any
-// time tau; a plain linear cut of the (tile, slice) pairs spreads the workgroups over all token offsets, every panel is then fetched
-// past the L2 by each of them: 294 us of slice loops at n = 4096 instead of 190).  nprim = 0, P = 0 is the plain linear cut of the
-// left-over tiles (taken when a helper range would touch more than three tiles: Sh > 2 (Ks - P)).
+// ---- the cut of a launch (shared by the host, the kernels and the CPU tests of the cut: tests/test_lib_loads.py through
+// ganq_debug_hessian_t_cut and ganq_debug_hessian_t_check).  T tiles of Ks token slices on G workgroups: W = T div G whole tiles per
+// workgroup first (tile w G + c: everybody walks the tokens of a row of tiles in step, the operand panels are shared in the L2). The R
+// = T mod G tiles left over are cut so that the workgroups still read the same tokens at the same time: workgroup c < nprim is the
+// PRIMARY of left-over tile c and takes its slices [0, P); the others are HELPERS that share the tails [P, Ks) of all left-over tiles
+// in equal contiguous ranges of Sh slices, each started at the tile boundary inside its range (primaries are at slice tau, helpers at P
+// + tau or P + tau - (Sh - Lt) at any time tau; a plain linear cut of the (tile, slice) pairs spreads the workgroups over all token
+// offsets, every panel is then fetched past the L2 by each of them: 294 us of slice loops at n = 4096 instead of 190).  nprim = 0, P =
+// 0 is the plain linear cut of the left-over tiles (taken when a helper range would touch more than three tiles: Sh > 2 (Ks - P), or
+// when the primaries would take every slice: P = Ks).  A plain cut with Sh = Ks leaves every left-over tile in ONE part, finished from
+// the registers like a whole tile (n = 4096, 64 tokens, 256 CUs: all 136 tiles); the fix kernel must not touch those (hw_fix_finishes).
 struct HwCut { int Ks, G, W, R, nprim, P, Sh; };
 struct HwSeg { int t, s0, s1, np, slot; };  // slices [s0, s1) of tile t: one of the tile's np parts, kept in slot `slot` of the workgroup's partial tiles when np > 1
 
@@ -125,6 +130,15 @@ __host__ __device__ inline int hw_parts_of(const HwCut& q, int r) {
     int hf;
     return (q.P > 0 ? 1 : 0) + hw_helpers_of(q, r, hf);
 }
+// whether hessian_w4_fix_kernel finishes left-over tile r: only a tile of two or more parts stored in partial slots.  A tile of one
+// part is finished by the main kernel from its registers and leaves no partial tile behind.
+__host__ __device__ inline bool hw_fix_finishes(const HwCut& q, int r) { return hw_parts_of(q, r) > 1; }
+// whether the fix kernel has any tile to finish (host: the launch is skipped otherwise; a plain cut with Sh = Ks has none)
+inline bool hw_fix_needed(const HwCut& q) {
+    for (int r = 0; r < q.R; ++r)
+        if (hw_fix_finishes(q, r)) return true;  // (primary cuts: at r = 0)
+    return false;
+}
 __host__ __device__ inline void hw_part_location(const HwCut& q, int r, int pi, int& wg, int& slot) {
     const int pb = q.P > 0 ? 1 : 0;
     wg = r;
@@ -138,9 +152,12 @@ __host__ __device__ inline void hw_part_location(const HwCut& q, int r, int pi, 
     }
 }
 
-// the left-over segments of workgroup c (at most three), in the order it works through them -> count
-__host__ __device__ inline int hw_left_segments(const HwCut& q, int c, HwSeg (&left)[3]) {
+// the left-over segments of workgroup c (at most three), in the order it works through them -> count.  `dropped` (the host check
+// only; the kernels pass nothing): slices of the workgroup's range that did not fit in three segments -- 0 for every cut
+// hw_make_cut makes (a helper range of Sh <= 2 (Ks - P) slices touches at most three tiles), asserted by ganq_debug_hessian_t_check.
+__host__ __device__ inline int hw_left_segments(const HwCut& q, int c, HwSeg (&left)[3], long long* dropped = nullptr) {
     int nleft = 0;
+    if (dropped) *dropped = 0;
     if (q.R <= 0) return 0;
     const int Lt = q.Ks - q.P, t0 = q.W * q.G;
     if (c < q.nprim) {
@@ -163,6 +180,11 @@ __host__ __device__ inline int hw_left_segments(const HwCut& q, int c, HwSeg (&l
             left[nleft++] = HwSeg{t0 + r, q.P + off, q.P + off + len, hw_parts_of(q, r), r - r0};
             pos += len;
         }
+    }
+    if (dropped) {
+        long long got = 0;
+        for (int k = 0; k < nleft; ++k) got += left[k].s1 - left[k].s0;
+        *dropped = (b - a) - got;
     }
     return nleft;
 }
@@ -235,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void hessian_w4_kernel(float* __restrict__ 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) hg_mfma_zero<BF16>(acc[i][j], z);
         }
-        __builtin_amdgcn_s_barrier();  // the previous segment's LDS reads (and its ticket word) are done in every wave
+        __builtin_amdgcn_s_barrier();  // the previous segment's LDS reads are done in every wave
 #ifdef HW_PROBE_ALIGN
         const char* const seg = xb;  // (timing experiment: every workgroup reads the same tokens -- wrong sums)
 #else
@@ -375,14 +397,16 @@ __global__ __launch_bounds__(256, 1) void hessian_w4_kernel(float* __restrict__ 
     }
 }
 
-// The left-over tiles: part sums in the order of the cut (the primary's, then the helpers' along the tails), then H <- H * decay +
-// scale * sum on the tile and its mirror image.  One workgroup per QUARTER of a tile (the 128 x 128 block one wave of the main kernel
-// held, 64 KB per part, register order: whole 1 KB lines per load instruction).  No atomics, no tickets: the kernel boundary is the
-// hand-over, the order is fixed, the result the same from run to run.
+// The left-over tiles of two or more parts (hw_fix_finishes; a workgroup of a one-part tile returns at once): part sums in the order
+// of the cut (the primary's, then the helpers' along the tails), then H <- H * decay + scale * sum on the tile and its mirror image.
+// One workgroup per QUARTER of a tile (the 128 x 128 block one wave of the main kernel held, 64 KB per part, register order: whole
+// 1 KB lines per load instruction).  No atomics, no tickets: the kernel boundary is the hand-over, the order is fixed, the result the
+// same from run to run.
 __global__ __launch_bounds__(256) void hessian_w4_fix_kernel(float* __restrict__ H, int n, float decay, float scale, const HwCut cut,
                                                             const float* __restrict__ partial, const uint32_t* __restrict__ table) {
     const int tid = threadIdx.x;
     const int r = (int)blockIdx.x >> 2, wvq = (int)blockIdx.x & 3;  // left-over tile, quarter (wr, wc)
+    if (!hw_fix_finishes(cut, r)) return;  // one part: the main kernel has finished it from its registers, no partial tile was stored
     const int t = cut.W * cut.G + r;
     int bu, bv;
     hw_tile_of(table, t, bu, bv);
@@ -447,8 +471,15 @@ bool hessian_w4_supported(int64_t n, int64_t ldt) {
     return nt * (nt + 1) / 2 <= W_MAX_TILES && n * ldt * 2 < ((int64_t)1 << 32) && opt_get(OPT_HESS_W4) != 0;
 }
 
+// workgroups of a launch: one per CU, or GANQ_HESS_W4_WGS (tests: the cuts of parts with other CU counts on this one -- the kernels
+// do not wait on each other across workgroups, more than CUs just queue).  The workspace is sized by the same number.
+static int hw_workgroups() {
+    const long long forced = opt_get(OPT_HESS_W4_WGS);
+    return forced > 0 ? (int)std::min<long long>(forced, 1 << 16) : std::max(1, current_device_cus());
+}
+
 size_t hessian_w4_workspace_bytes(int64_t n) {
-    return (size_t)W_MAX_TILES * sizeof(int) + (size_t)std::max(1, current_device_cus()) * W_SLOTS * W_PART * sizeof(float);
+    return (size_t)W_MAX_TILES * sizeof(int) + (size_t)hw_workgroups() * W_SLOTS * W_PART * sizeof(float);
 }
 
 // the staging copy of one batch: Xt[:, tok0 : tok0 + rows] = X^T
@@ -473,11 +504,10 @@ int hessian_w4(float* H, const void* Xt, int64_t ldt, int dtype, int64_t rows, i
     const size_t need = hessian_w4_workspace_bytes(n);
     if (!workspace || workspace_bytes < need) return fail(-4, "ganq_hessian_accum_t: workspace %zu B < required %zu B", workspace_bytes, need);
     if ((reinterpret_cast<uintptr_t>(Xt) & 15) != 0 || (reinterpret_cast<uintptr_t>(H) & 15) != 0) return fail(-3, "ganq_hessian_accum_t: 16-byte aligned buffers expected");
-    const int ncu = std::max(1, current_device_cus());
     const int64_t nt = (n + WT - 1) / WT;
     const int64_t T = nt * (nt + 1) / 2;
     const int64_t Ks = rows / WSK;
-    const HwCut cut = hw_make_cut(T, Ks, ncu);
+    const HwCut cut = hw_make_cut(T, Ks, hw_workgroups());  // (the G the workspace was sized for: checked above)
     const int nwg = cut.G, R = cut.R;
     int tcount = 0;
     const uint32_t* table = hessian_tile_table((int)nt, &tcount);
@@ -494,7 +524,7 @@ int hessian_w4(float* H, const void* Xt, int64_t ldt, int dtype, int64_t rows, i
         if (rc) return rc;
         hipLaunchKernelGGL(hessian_w4_kernel<false>, dim3((unsigned)nwg), dim3(256), lds, stream, H, Xp, (int)ldt, (int)n, decay, scale, cut, partial, table);
     }
-    if (R > 0)
+    if (R > 0 && hw_fix_needed(cut))  // (not when every left-over tile is in one part: nothing was stored)
         hipLaunchKernelGGL(hessian_w4_fix_kernel, dim3((unsigned)(4 * R)), dim3(256), 0, stream, H, (int)n, decay, scale, cut, partial, table);
     GANQ_LAUNCH_CHECK();
     return 0;
@@ -504,7 +534,8 @@ int hessian_w4(float* H, const void* Xt, int64_t ldt, int dtype, int64_t rows, i
 
 /* tests (no GPU needed): the cut of ganq_hessian_accum_t for in_features n, `rows` tokens on `ncu` workgroups, by the code the kernels
  * run.  hdr[7] = {Ks, G, W, R, nprim, P, Sh}; segs = [ncu][W + 3][5] ints {tile, s0, s1, parts, slot}, unused entries tile = -1;
- * parts_loc = [R][max_parts][2] ints {workgroup, slot} of every left-over tile's parts in the order they are summed (-1 padded). */
+ * parts_loc = [R][max_parts][2] ints {workgroup, slot} of the parts hessian_w4_fix_kernel sums for each left-over tile, in the order
+ * it sums them (-1 padded; all -1 for a tile it does not finish, hw_fix_finishes). */
 extern "C" int ganq_debug_hessian_t_cut(int64_t n, int64_t rows, int ncu, int* hdr, int* segs, int segs_cap, int* parts_loc, int max_parts) {
     using namespace ganq;
     if (n <= 0 || rows <= 0 || (rows % WSK) != 0 || ncu <= 0 || !hdr) return fail(-1, "ganq_debug_hessian_t_cut: bad arguments");
@@ -529,7 +560,7 @@ extern "C" int ganq_debug_hessian_t_cut(int64_t n, int64_t rows, int ncu, int* h
     }
     if (parts_loc) {
         for (int r = 0; r < q.R; ++r) {
-            const int np = hw_parts_of(q, r);
+            const int np = hw_fix_finishes(q, r) ? hw_parts_of(q, r) : 0;
             for (int pi = 0; pi < max_parts; ++pi) {
                 int wg = -1, sl = -1;
                 if (pi < np) hw_part_location(q, r, pi, wg, sl);
@@ -538,6 +569,74 @@ extern "C" int ganq_debug_hessian_t_cut(int64_t n, int64_t rows, int ncu, int* h
             }
         }
     }
+    return 0;
+}
+
+/* tests (no GPU needed): the properties of that cut, checked on the code the kernels and the host run -> 0, or the first violated one:
+ *   -11  a (tile, token slice) pair covered by no segment or by more than one (or a segment outside the tiles / slices)
+ *   -12  slices of a workgroup's range dropped by the three-segment cap of hw_left_segments
+ *   -13  a part of a tile of two or more parts that stores no partial tile, a slot outside [0, W_SLOTS) or taken twice by one
+ *        workgroup, or a part list of the fix kernel (hw_part_location) that does not name the tile's segments in slice order
+ *   -14  the tiles the fix kernel finishes (hw_fix_finishes; its launch: hw_fix_needed) are not exactly the left-over tiles of two or
+ *        more parts */
+extern "C" int ganq_debug_hessian_t_check(int64_t n, int64_t rows, int ncu) {
+    using namespace ganq;
+    if (n <= 0 || rows <= 0 || (rows % WSK) != 0 || ncu <= 0) return fail(-1, "ganq_debug_hessian_t_check: bad arguments");
+    const int64_t nt = (n + WT - 1) / WT, T = nt * (nt + 1) / 2;
+    const HwCut q = hw_make_cut(T, rows / WSK, ncu);
+    const int64_t t0 = (int64_t)q.W * q.G;
+    if (t0 + q.R != T) return fail(-11, "ganq_debug_hessian_t_check: %lld whole + %d left-over tiles of %lld", (long long)t0, q.R, (long long)T);
+    std::vector<int> whole((size_t)t0, 0);  // the kernel's whole tiles: k G + c, k < W
+    for (int c = 0; c < q.G; ++c)
+        for (int k = 0; k < q.W; ++k) ++whole[(size_t)k * q.G + c];
+    for (int64_t t = 0; t < t0; ++t)
+        if (whole[(size_t)t] != 1) return fail(-11, "ganq_debug_hessian_t_check: whole tile %lld taken %d times", (long long)t, whole[(size_t)t]);
+    struct Part { int s0, s1, c, slot, np; };
+    std::vector<std::vector<Part>> parts((size_t)q.R);
+    for (int c = 0; c < q.G; ++c) {
+        HwSeg left[3];
+        long long dropped = 0;
+        const int nl = hw_left_segments(q, c, left, &dropped);
+        if (dropped != 0) return fail(-12, "ganq_debug_hessian_t_check: workgroup %d drops %lld slices", c, dropped);
+        bool used[W_SLOTS] = {};
+        for (int k = 0; k < nl; ++k) {
+            const HwSeg& sg = left[k];
+            const int64_t r = sg.t - t0;
+            if (r < 0 || r >= q.R || sg.s0 < 0 || sg.s0 >= sg.s1 || sg.s1 > q.Ks)
+                return fail(-11, "ganq_debug_hessian_t_check: workgroup %d segment tile %d slices [%d, %d)", c, sg.t, sg.s0, sg.s1);
+            if (sg.np > 1) {
+                if (sg.slot < 0 || sg.slot >= W_SLOTS || used[sg.slot]) return fail(-13, "ganq_debug_hessian_t_check: workgroup %d slot %d", c, sg.slot);
+                used[sg.slot] = true;
+            }
+            parts[(size_t)r].push_back(Part{sg.s0, sg.s1, c, sg.slot, sg.np});
+        }
+    }
+    bool any_fix = false;
+    for (int r = 0; r < q.R; ++r) {
+        std::vector<Part>& pr = parts[(size_t)r];
+        std::sort(pr.begin(), pr.end(), [](const Part& a, const Part& b) { return a.s0 < b.s0; });
+        int pos = 0;
+        for (const Part& p : pr) {
+            if (p.s0 != pos) return fail(-11, "ganq_debug_hessian_t_check: left-over tile %d: slice %d covered %s", r, std::min(pos, p.s0), p.s0 > pos ? "by nobody" : "twice");
+            pos = p.s1;
+        }
+        if (pos != q.Ks) return fail(-11, "ganq_debug_hessian_t_check: left-over tile %d: slices from %d on covered by nobody", r, pos);
+        const int cnt = (int)pr.size();
+        for (const Part& p : pr)  // np > 1 <=> the segment stores its partial tile
+            if (p.np != cnt) return fail(-13, "ganq_debug_hessian_t_check: left-over tile %d: %d parts, a segment says %d", r, cnt, p.np);
+        if (hw_parts_of(q, r) != cnt) return fail(-13, "ganq_debug_hessian_t_check: left-over tile %d: %d parts, hw_parts_of %d", r, cnt, hw_parts_of(q, r));
+        if (hw_fix_finishes(q, r) != (cnt >= 2)) return fail(-14, "ganq_debug_hessian_t_check: left-over tile %d of %d parts, fix kernel %d", r, cnt, (int)hw_fix_finishes(q, r));
+        if (cnt < 2) continue;
+        any_fix = true;
+        for (int pi = 0; pi < cnt; ++pi) {
+            int wg = -1, sl = -1;
+            hw_part_location(q, r, pi, wg, sl);
+            if (wg != pr[(size_t)pi].c || sl != pr[(size_t)pi].slot)
+                return fail(-13, "ganq_debug_hessian_t_check: left-over tile %d part %d: fix kernel reads (%d, %d), stored at (%d, %d)", r, pi, wg, sl,
+                            pr[(size_t)pi].c, pr[(size_t)pi].slot);
+        }
+    }
+    if (hw_fix_needed(q) != any_fix) return fail(-14, "ganq_debug_hessian_t_check: fix launch %d, tiles of two or more parts %d", (int)hw_fix_needed(q), (int)any_fix);
     return 0;
 }
 

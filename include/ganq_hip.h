@@ -81,7 +81,8 @@ int ganq_hessian_accum(float* H, const void* X, int dtype, int64_t rows, int64_t
  * rows of accum_t: a multiple of 32 (the host zero-fills the columns of a ragged last slice); tok0, rows of stage_t and
  * n: multiples of 8.  ganq_hessian_t_supported(n, ldt) says whether a layer is served (in_features >= 3072, a multiple
  * of 8, n * ldt * 2 B < 4 GiB); otherwise the host stages row-major and calls ganq_hessian_accum.  workspace:
- * ganq_hessian_t_workspace_bytes(n) of caller-owned scratch (ticket counters + two partial tiles per compute unit).
+ * ganq_hessian_t_workspace_bytes(n) of caller-owned scratch (three partial tiles per workgroup of the launch: one per
+ * compute unit, or option GANQ_HESS_W4_WGS; sized at the call's option value).
  * Same products as ganq_hessian_accum, another grouping of the fp32 sums; exactly symmetric; deterministic.       */
 int ganq_hessian_t_supported(int64_t n, int64_t ldt);
 size_t ganq_hessian_t_workspace_bytes(int64_t n);
@@ -90,8 +91,13 @@ int ganq_hessian_accum_t(float* H, const void* Xt, int64_t ldt, int dtype, int64
                          int64_t batch, void* workspace, size_t workspace_bytes, void* stream);
 /* tests (host only, no GPU): how ganq_hessian_accum_t cuts its (tile, token slice) pairs over `ncu` workgroups, computed by
  * the code the kernels run.  hdr[7] = {Ks, G, W, R, nprim, P, Sh}; segs [ncu][W + 3][5] = {tile, s0, s1, parts, slot}
- * (tile -1: unused); parts_loc [R][max_parts][2] = {workgroup, slot} of a left-over tile's parts in summation order. */
+ * (tile -1: unused); parts_loc [R][max_parts][2] = {workgroup, slot} of the parts the fix kernel sums for a left-over tile, in
+ * summation order (-1 padded; all -1 for a tile of one part, which the main kernel finishes and the fix kernel leaves alone). */
 int ganq_debug_hessian_t_cut(int64_t n, int64_t rows, int ncu, int* hdr, int* segs, int segs_cap, int* parts_loc, int max_parts);
+/* tests (host only): the properties of that cut -> 0, or a negative code for the first violated one: -11 a (tile, slice) pair not
+ * covered exactly once, -12 slices dropped by the three-segment cap, -13 a part of a multi-part tile without a distinct partial slot
+ * or not where the fix kernel reads it, -14 the tiles the fix kernel finishes are not exactly the left-over tiles of >= 2 parts. */
+int ganq_debug_hessian_t_check(int64_t n, int64_t rows, int ncu);
 
 /* ---- a2: prologue (gptq.py:280-309) -- lower Cholesky factor A = L L^T in fp32, in place (row-major, leading
  * dimension lda; the strictly upper triangle is zeroed like torch.linalg.cholesky does).  *info (device int32) is 0

@@ -132,8 +132,8 @@ def test_hessian_token_split_launches(hip, rows, n, dtype, lib_options):
                                           (2048, 4096, torch.float16), (40, 1024, torch.float16)])
 def test_hessian_transposed_staging_stream_k(hip, rows, n, dtype, lib_options):
     """hessian_w4.hip: the batches of a group staged TRANSPOSED (hessian_stage_t, one call per batch) and multiplied as Xt Xt^T with
-    256 x 256 tiles, the (tile, token slice) pairs cut into equal shares, one per CU; partial tiles meet through a ticket and are
-    summed in range order.  Against the fp64 product and the row-major kernels (same products, another grouping of the fp32 sums);
+    256 x 256 tiles, the (tile, token slice) pairs cut stream-K over one workgroup per CU; the parts of a tile cut in several are
+    stored as partial tiles and summed in the order of the cut by a second launch (hessian_w4_fix_kernel).  Against the fp64 product and the row-major kernels (same products, another grouping of the fp32 sums);
     exactly symmetric; the same bits from run to run whichever workgroup finishes a tile; the running average's decay applied
     once; in_features that are not a multiple of the tile (1288), token counts that are not a multiple of the slice (4128 -> the
     host zero-fills, 40), a group that fills only part of the staging buffer."""

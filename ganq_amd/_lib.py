@@ -82,6 +82,12 @@ SIGNATURES = {
     "ganq_lut_linear_outliers_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_linear_fwd_outliers": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64,
                                                     _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_linear_bwd_input_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_linear_bwd_input": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp,
+                                                 _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_linear_bwd_lut_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_linear_bwd_lut": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp,
+                                               _c_sz, _c_vp]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_outlier_cutoffs": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_extract": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -717,3 +723,61 @@ def lut_linear(x, qweight, lut, bias, bits: int, addend=None):
     _call("ganq_lut_linear_fwd", (x, qweight, lut, bias, y, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias), code, M, m, n, bits,
                                      y.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
     return y
+
+
+_BWD_CHUNK_BYTES = 1 << 31  # activations per backward call (tests lower it to exercise the chunking)
+
+
+def _bwd_max_rows(width: int) -> int:
+    """rows of a [rows, width] 16-bit activation per call: ~2 GB, as lut_linear splits x"""
+    return max(256, ((_BWD_CHUNK_BYTES - 1) // (2 * max(width, 1)) - 256) // 256 * 256)
+
+
+def lut_linear_bwd_input(dy, qweight, lut, bits: int, addend=None):
+    """dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend fp32 [M,n]), fp32 accumulation and one rounding to dy's dtype.
+    dy fp16/bf16 [M,m], qweight int32 [n*bits/32, m], lut [m,V] in dy's dtype."""
+    code = _act_dtype(dy, "dy")
+    if lut.dtype != dy.dtype:
+        raise GanqHipError("dy and lut must share one dtype")
+    dy, qweight, lut = dy.contiguous(), qweight.contiguous(), lut.contiguous()
+    M, m = dy.shape
+    n = qweight.shape[0] * 32 // bits
+    if lut.shape[0] != m or qweight.shape[1] != m:
+        raise GanqHipError("lut_linear_bwd_input: dy, qweight and lut disagree on out_features")
+    if addend is not None and (addend.dtype != torch.float32 or tuple(addend.shape) != (M, n)):
+        raise GanqHipError("lut_linear_bwd_input: addend must be fp32 [M, in_features]")
+    step = _bwd_max_rows(max(m, n))
+    if M > step:  # row chunks are independent
+        return torch.cat([lut_linear_bwd_input(dy[r:r + step], qweight, lut, bits, None if addend is None else addend[r:r + step])
+                          for r in range(0, M, step)], dim=0)
+    if addend is not None:
+        addend = addend.contiguous()
+    dx = torch.empty((M, n), dtype=dy.dtype, device=dy.device)
+    ws = _workspace(lib().ganq_lut_linear_bwd_input_workspace_bytes(M, m, n, bits), dy.device)
+    _call("ganq_lut_linear_bwd_input", (dy, qweight, lut, addend, dx, ws), dy.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(addend), code,
+          M, m, n, bits, dx.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return dx
+
+
+def lut_linear_bwd_lut(dy, x, qweight, bits: int, m: int):
+    """dlut fp32 [m, 2^bits]: dlut[o][v] = sum over rows b and input features j with Q[o][j] == v of dy[b][o] * x[b][j].
+    dy [M,m], x [M,n] fp16/bf16 (one dtype), qweight int32 [n*bits/32, m].  Codes no index uses get exactly 0."""
+    code = _act_dtype(dy, "dy")
+    if x.dtype != dy.dtype:
+        raise GanqHipError("dy and x must share one dtype")
+    dy, x, qweight = dy.contiguous(), x.contiguous(), qweight.contiguous()
+    M, n = x.shape
+    if dy.shape != (M, m) or qweight.shape != (n * bits // 32, m):
+        raise GanqHipError("lut_linear_bwd_lut: dy [M,m], x [M,n] and qweight [n*bits/32, m] disagree")
+    step = _bwd_max_rows(max(m, n))
+    if M > step:  # chunk sums are added in chunk order
+        out = None
+        for r in range(0, M, step):
+            part = lut_linear_bwd_lut(dy[r:r + step], x[r:r + step], qweight, bits, m)
+            out = part if out is None else out + part
+        return out
+    dlut = torch.empty((m, 1 << bits), dtype=torch.float32, device=dy.device)
+    ws = _workspace(lib().ganq_lut_linear_bwd_lut_workspace_bytes(M, m, n, bits), dy.device)
+    _call("ganq_lut_linear_bwd_lut", (dy, x, qweight, dlut, ws), dy.data_ptr(), x.data_ptr(), qweight.data_ptr(), code, M, m, n, bits,
+          dlut.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return dlut

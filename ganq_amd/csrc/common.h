@@ -95,6 +95,10 @@ bool gemm_h16_supported(int64_t M, int64_t N, int64_t K);
 int gemm_h16(const void* x, const void* w, const void* bias, const float* addend, int dtype, int64_t M, int64_t N, int64_t K, void* y,
              hipStream_t stream);
 
+// the same kernel with the codebook-gradient epilogue (lut_backward.hip): bpart [ceil(N / 256)][M][2^bits] fp32
+int gemm_h16_buckets(const void* xt, const void* wt, const uint32_t* qw, int bits, int dtype, int64_t M, int64_t N, int64_t K, float* bpart,
+                     hipStream_t stream);
+
 // Hessian of staged groups from TRANSPOSED activations Xt [in_features][ldt tokens], 256 x 256 tiles cut stream-K (hessian_w4.hip)
 const uint32_t* hessian_tile_table(int tiles, int* count);  // device table of the lower-triangular tile pairs (tu << 16 | tv), Z order
 bool hessian_w4_supported(int64_t n, int64_t ldt);
@@ -124,6 +128,8 @@ enum KernelId : int {
     KID_T_PREP,
     KID_T_INCR,
     KID_CHOLESKY,
+    KID_LUT_BWD_INPUT,
+    KID_LUT_BWD_LUT,
     KID_COUNT
 };
 bool profile_enabled(int kid);

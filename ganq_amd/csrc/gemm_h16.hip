@@ -61,10 +61,72 @@ __device__ __forceinline__ void hg_tile_of(int bid, int tiles_m, int tiles_n, in
     tm = p * HG_PANEL + (idx - tn * ph);
 }
 
-template <bool BF16, int BM>
+// Codebook-gradient epilogue (BBITS = 2 / 3 / 4).  A lane holds G[o][j .. j + 3] for MT rows o of its wave tile and four groups of
+// four columns j.  Per row: the lane decodes the four codes Q[o][j .. j + 3] from qw[j * BBITS / 32][o], adds each product into its
+// 2^BBITS bins by compare-select (columns ascending), the four lanes of the row combine their bins by two butterfly steps (the same
+// sum in all four: IEEE addition commutes), each writes a quarter of them to LDS, and after a barrier the workgroup sums its four
+// column waves in order.  Nothing but the selected products enters a bin: a code no index of the tile uses gets exactly 0.
+template <int BM, int BBITS, int MT = BM / 32>
+__device__ __forceinline__ void hg_bucket_epilogue(const hg_f32x4 (&acc)[MT][4], const uint32_t* __restrict__ qw, float* __restrict__ bpart,
+                                                   int M, int N, int row0, int f0, int tn, int wr, int wc, int lane, int tid) {
+    constexpr int V = 1 << BBITS, VQ = V / 4;
+    extern __shared__ __align__(1024) char hg_smem[];
+    float* red = reinterpret_cast<float*>(hg_smem);  // [BM rows][4 column waves][V]  (64 KB at BM = 256, V = 16)
+    __syncthreads();  // every wave is done with the operand tiles
+    const int fq = (lane >> 4) * 4, g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {  // (unrolled: acc is only addressable with constant indices)
+        const int rl = wr * (BM / 2) + i * 16 + (lane & 15);
+        const int o = min(row0 + rl, M - 1);
+        float bins[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) bins[v] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int f = f0 + wc * 64 + j * 16 + fq;
+            if (f >= N) continue;
+            const int bitpos = f * BBITS, wi = bitpos >> 5, sh = bitpos & 31;
+            uint64_t word = qw[(int64_t)wi * M + o];
+            if (sh + 4 * BBITS > 32) word |= (uint64_t)qw[(int64_t)(wi + 1) * M + o] << 32;
+            const uint32_t codes = (uint32_t)(word >> sh);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t c = (codes >> (BBITS * r)) & (uint32_t)(V - 1);
+#pragma unroll
+                for (int v = 0; v < V; ++v) bins[v] += (c == (uint32_t)v) ? acc[i][j][r] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            bins[v] += __shfl_xor(bins[v], 16);
+            bins[v] += __shfl_xor(bins[v], 32);
+        }
+#pragma unroll
+        for (int q = 0; q < VQ; ++q) {
+            float b = bins[q];
+#pragma unroll
+            for (int gg = 1; gg < 4; ++gg)
+                if (g == gg) b = bins[gg * VQ + q];
+            red[(rl * 4 + wc) * V + g * VQ + q] = b;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < BM * V; e += HTHREADS) {
+        const int rl = e / V, v = e - rl * V, o = row0 + rl;
+        if (o >= M) continue;
+        const float* rr = red + rl * 4 * V + v;
+        bpart[((int64_t)tn * M + o) * V + v] = ((rr[0] + rr[V]) + rr[2 * V]) + rr[3 * V];
+    }
+}
+
+// BBITS = 0: the dense store below.  BBITS = 2 / 3 / 4: the codebook-gradient epilogue of lut_backward.hip -- y is not written; x is
+// dy^T [m][tokens], w is X^T [n][tokens], and the tile's fp32 products G[o][j] are summed into the 2^BBITS bins of the codes
+// Q[o][j] (decoded from qw, the layer's packed indices), one fp32 partial bpart[tile column][o][code] per workgroup.
+template <bool BF16, int BM, int BBITS>
 __global__ __launch_bounds__(HTHREADS, 1) void gemm_h16_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
                                                               const uint16_t* __restrict__ bias, const float* __restrict__ addend,
-                                                              int M, int N, int K, int tiles_m, int tiles_n, uint16_t* __restrict__ y) {
+                                                              int M, int N, int K, int tiles_m, int tiles_n, uint16_t* __restrict__ y,
+                                                              const uint32_t* __restrict__ qw, float* __restrict__ bpart) {
     constexpr int MT = BM / 32;        // 16-row tiles of the wave tile (BM / 2 rows): 8 or 4
     constexpr int MH = MT / 2;         // ... per phase (one half of the wave's rows)
     constexpr int GLA = BM / 128;      // LDS-DMA instructions per thread for one HALF of the x tile (BM / 2 rows x 128 B)
@@ -257,6 +319,10 @@ __global__ __launch_bounds__(HTHREADS, 1) void gemm_h16_kernel(const uint16_t* _
 
     // ---- epilogue: acc[i][j][r] = y[row0 + wr BM/2 + 16 i + (l & 15)][f0 + 64 wc + 16 j + 4 (l >> 4) + r]
     const int fq = (lane >> 4) * 4;
+    if constexpr (BBITS > 0) {
+        hg_bucket_epilogue<BM, BBITS>(acc, qw, bpart, M, N, row0, f0, tn, wr, wc, lane, tid);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int f = f0 + wc * 64 + j * 16 + fq;
@@ -527,10 +593,10 @@ int gemm_h16(const void* x, const void* w, const void* bias, const float* addend
 #define GANQ_H16_LAUNCH(BF, BMV)                                                                                                    \
     do {                                                                                                                            \
         const int tiles_m = (int)((M + BMV - 1) / BMV);                                                                             \
-        int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_h16_kernel<BF, BMV>), hg_lds_bytes<BMV>());                  \
+        int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_h16_kernel<BF, BMV, 0>), hg_lds_bytes<BMV>());                  \
         if (rc_) return rc_;                                                                                                        \
-        hipLaunchKernelGGL((gemm_h16_kernel<BF, BMV>), dim3((unsigned)(tiles_m * tiles_n)), dim3(HTHREADS), hg_lds_bytes<BMV>(), stream, \
-                           xp, wp, bp, addend, (int)M, (int)N, (int)K, tiles_m, tiles_n, yp);                                        \
+        hipLaunchKernelGGL((gemm_h16_kernel<BF, BMV, 0>), dim3((unsigned)(tiles_m * tiles_n)), dim3(HTHREADS), hg_lds_bytes<BMV>(), stream, \
+                           xp, wp, bp, addend, (int)M, (int)N, (int)K, tiles_m, tiles_n, yp, nullptr, nullptr);                      \
     } while (0)
     if (dtype == 1) {
         if (big) GANQ_H16_LAUNCH(true, 256);
@@ -540,6 +606,45 @@ int gemm_h16(const void* x, const void* w, const void* bias, const float* addend
         else GANQ_H16_LAUNCH(false, 128);
     }
 #undef GANQ_H16_LAUNCH
+    GANQ_LAUNCH_CHECK();
+    return 0;
+}
+
+// codebook gradient (lut_backward.hip): bpart [ceil(N / 256)][M][2^bits] fp32 = per 256-column tile, the bins of
+// G = xt [M, K] @ wt [N, K]^T by the codes of qw [N * bits / 32][M].  Same tiles and main loop as gemm_h16.
+int gemm_h16_buckets(const void* xt, const void* wt, const uint32_t* qw, int bits, int dtype, int64_t M, int64_t N, int64_t K, float* bpart,
+                     hipStream_t stream) {
+    if (!gemm_h16_supported(M, N, K)) return fail(-1, "gemm_h16_buckets: shape %lld x %lld x %lld not supported", (long long)M, (long long)N, (long long)K);
+    const int ncu = std::max(1, current_device_cus());
+    const int tiles_n = (int)((N + HBN - 1) / HBN);
+    const int64_t t256 = ((M + 255) / 256) * tiles_n;
+    const long long force = opt_get(OPT_GEMM_H16_BM);
+    const bool big = force > 0 ? force >= 256 : 8 * t256 >= 7 * ncu;
+    const uint16_t* xp = static_cast<const uint16_t*>(xt);
+    const uint16_t* wp = static_cast<const uint16_t*>(wt);
+#define GANQ_H16B_LAUNCH(BF, BMV, BB)                                                                                                 \
+    do {                                                                                                                              \
+        const int tiles_m = (int)((M + BMV - 1) / BMV);                                                                               \
+        int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_h16_kernel<BF, BMV, BB>), hg_lds_bytes<BMV>());                \
+        if (rc_) return rc_;                                                                                                          \
+        hipLaunchKernelGGL((gemm_h16_kernel<BF, BMV, BB>), dim3((unsigned)(tiles_m * tiles_n)), dim3(HTHREADS), hg_lds_bytes<BMV>(), stream, \
+                           xp, wp, nullptr, nullptr, (int)M, (int)N, (int)K, tiles_m, tiles_n, nullptr, qw, bpart);                    \
+    } while (0)
+#define GANQ_H16B_BITS(BF, BMV)                            \
+    do {                                                   \
+        if (bits == 2) GANQ_H16B_LAUNCH(BF, BMV, 2);       \
+        else if (bits == 3) GANQ_H16B_LAUNCH(BF, BMV, 3);  \
+        else GANQ_H16B_LAUNCH(BF, BMV, 4);                 \
+    } while (0)
+    if (dtype == 1) {
+        if (big) GANQ_H16B_BITS(true, 256);
+        else GANQ_H16B_BITS(true, 128);
+    } else {
+        if (big) GANQ_H16B_BITS(false, 256);
+        else GANQ_H16B_BITS(false, 128);
+    }
+#undef GANQ_H16B_BITS
+#undef GANQ_H16B_LAUNCH
     GANQ_LAUNCH_CHECK();
     return 0;
 }

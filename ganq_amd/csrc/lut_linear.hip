@@ -12,6 +12,7 @@
 //   M > 64: lut_gemm.hip (fused LUT-dequant GEMM).
 // ganq_lut_dequant: materialises W_q [m,n] in the activation dtype (dequantize_weight(), tests, A/B runs against a library GEMM).
 #include "common.h"
+#include "lut_bits.h"
 
 namespace ganq {
 
@@ -23,16 +24,6 @@ __device__ __forceinline__ float load_act(const void* p, int64_t i, int dtype) {
 __device__ __forceinline__ uint16_t store_act(float v, int dtype) {
     if (dtype == 1) return __builtin_bit_cast(uint16_t, (__bf16)v);
     return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-
-// extract element j (0..31) of a 32-element group from its BITS words
-template <int BITS>
-__device__ __forceinline__ uint32_t extract(const uint32_t (&w)[BITS], int j) {
-    const int bitpos = BITS * j;
-    const int wi = bitpos >> 5, sh = bitpos & 31;
-    uint32_t v = w[wi] >> sh;
-    if (sh + BITS > 32) v |= w[wi + 1 < BITS ? wi + 1 : wi] << (32 - sh);
-    return v & ((1u << BITS) - 1u);
 }
 
 constexpr int LW = 4;          // waves per workgroup

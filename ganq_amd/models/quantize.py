@@ -104,7 +104,9 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
     modules = {n: {"bits": m.bits, "in_features": m.in_features, "out_features": m.out_features,
                    "bias": m.bias is not None, "outliers": int(getattr(m, "outliers", 0))}
                for n, m in model.named_modules() if isinstance(m, GanqHipQuantLinear)}
-    state = {k: v.detach().contiguous().cpu() for k, v in model.state_dict().items()}
+    # the codebook is stored as fp16 also while it trains as an fp32 parameter (train_codebook): the format does not change
+    luts = {f"{n}.lut" for n in modules}
+    state = {k: (v.detach().to(torch.float16) if k in luts else v.detach()).contiguous().cpu() for k, v in model.state_dict().items()}
     # tied weights (lm_head <-> embeddings) share storage: safetensors wants each tensor once
     seen, out = {}, {}
     for k, v in state.items():

@@ -11,6 +11,13 @@ With the outlier split (`QuantizeConfig.ganq_outlier_ratio`, paper section 3.3) 
   outlier_rowptr int32 [out_features + 1], outlier_cols int32 [nnz], outlier_vals fp16 [nnz]   (CSR by output feature)
 and `forward` == `F.linear(x, lut.gather(1, Q) + W_sparse, bias)`.
 
+Training (the reference's FakeQuantLinear is an F.linear on a buffer, so autograd reaches its input): with grad mode on and
+`x` or `lut` requiring grad, `forward` goes through `_GanqLutLinearFn`, whose backward runs the HIP kernels of
+csrc/lut_backward.hip -- dx = dy @ (Wq + W_sparse) (one rounding) and, after `train_codebook(True)`,
+dlut[o][v] = sum of dy[b][o] x[b][j] over the j with Q[o][j] == v.  `qweight` (the indices), `bias` and the outlier values
+are frozen buffers: they never receive a gradient.  Otherwise (inference, no_grad) `forward` makes exactly the call it
+always made: same launches, no grad_fn.
+
 `pack()` keeps the reference signature `(linear, scales, zeros, g_idx)` (utils/model.py:552-570): because that
 call only carries the dequantised nn.Linear, the indices/codebook are either passed by keyword
 (`ganq_indices=`, `ganq_codebook=`, what ganq_amd's processor does) or recovered from the weight itself -- a
@@ -32,7 +39,7 @@ class GanqHipQuantLinear(BaseQuantLinear):
     SUPPORTS_DESC_ACT = [True, False]
     SUPPORTS_SYM = [True, False]
     SUPPORTS_SHARDS = True
-    SUPPORTS_TRAINING = False
+    SUPPORTS_TRAINING = True
     SUPPORTS_AUTO_PADDING = False
     SUPPORTS_IN_FEATURES_DIVISIBLE_BY = [32]
     SUPPORTS_OUT_FEATURES_DIVISIBLE_BY = [1]
@@ -125,23 +132,97 @@ class GanqHipQuantLinear(BaseQuantLinear):
         Wq = _lib.lut_dequant(self.qweight, self.lut, self.in_features, self.bits)
         return Wq + self._sparse_dense(Wq.dtype) if self.outliers else Wq
 
+    def train_codebook(self, enabled: bool = True):
+        """enabled: `lut` becomes an fp32 nn.Parameter (the master copy; each forward rounds it to the activation dtype and
+        its gradient passes straight through that rounding).  False: back to an fp16 buffer, rounded once.  The name and so
+        the state_dict key stay `lut`."""
+        lut = self.lut.detach()
+        delattr(self, "lut")
+        if enabled:
+            self.lut = nn.Parameter(lut.to(torch.float32).clone())
+        else:
+            self.register_buffer("lut", lut.to(torch.float16).contiguous())
+        return self
+
+    def _outliers_t(self, dtype):
+        """W_sparse^T as CSR by input feature (rowptr [n+1], cols = output features, vals in `dtype`), built once on the device
+        (nnz = self.outliers is known: no host read) and cached; vals follow the buffer if it is replaced"""
+        cache = getattr(self, "_csr_t", None)
+        key = (self.outlier_cols.data_ptr(), self.outlier_vals.data_ptr(), self.outlier_rowptr.data_ptr())
+        if cache is None or cache[0] != key:
+            dev = self.outlier_cols.device
+            m, n, nnz = self.out_features, self.in_features, self.outliers
+            counts = (self.outlier_rowptr[1:] - self.outlier_rowptr[:-1]).long()
+            rows = torch.repeat_interleave(torch.arange(m, device=dev), counts, output_size=nnz)
+            cols = self.outlier_cols.long()
+            order = torch.argsort(cols * m + rows)
+            rowptr_t = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            rowptr_t.index_add_(0, cols + 1, torch.ones_like(cols))
+            rowptr_t = torch.cumsum(rowptr_t, 0).to(torch.int32)
+            cache = (key, rowptr_t, rows[order].to(torch.int32).contiguous(), order, {})
+            self._csr_t = cache
+        _, rowptr_t, cols_t, order, vals_by_dtype = cache
+        if dtype not in vals_by_dtype:
+            vals_by_dtype[dtype] = self.outlier_vals[order].to(dtype).contiguous()
+        return rowptr_t, cols_t, vals_by_dtype[dtype]
+
+    def _lut_forward(self, x2: torch.Tensor, lut: torch.Tensor, bias):
+        # one C-ABI entry for every batch size: the decode kernels up to 64 rows, the fused LUT-dequant GEMM above
+        # (csrc/lut_gemm.hip) -- the dequantised weight is never materialised and no library GEMM is called
+        if self.outliers:  # x @ W_sparse^T in fp32, added inside the LUT kernel before its one rounding
+            vals = self.outlier_vals if self.outlier_vals.dtype == x2.dtype else self.outlier_vals.to(x2.dtype)
+            return _lib.lut_linear_outliers(x2, self.qweight, lut, bias, self.bits, self.outlier_rowptr, self.outlier_cols, vals)
+        return _lib.lut_linear(x2, self.qweight, lut, bias, self.bits)
+
     def forward(self, x: torch.Tensor):
         if not x.is_cuda:
             raise _lib.GanqHipError("GanqHipQuantLinear runs on the GPU only (no CPU fallback)")
+        out_shape = x.shape[:-1] + (self.out_features,)
+        x2 = x.reshape(-1, self.in_features)
+        if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad):
+            return _GanqLutLinearFn.apply(x2, self.lut, self).reshape(out_shape)
         lut, bias = self.lut, self.bias
         if lut.dtype != x.dtype:
             lut = lut.to(x.dtype)
             bias = None if bias is None else bias.to(x.dtype)
-        out_shape = x.shape[:-1] + (self.out_features,)
-        x2 = x.reshape(-1, self.in_features)
-        # one C-ABI entry for every batch size: the decode kernels up to 64 rows, the fused LUT-dequant GEMM above
-        # (csrc/lut_gemm.hip) -- the dequantised weight is never materialised and no library GEMM is called
-        if self.outliers:  # x @ W_sparse^T in fp32, added inside the LUT kernel before its one rounding
-            vals = self.outlier_vals if self.outlier_vals.dtype == x.dtype else self.outlier_vals.to(x.dtype)
-            y = _lib.lut_linear_outliers(x2, self.qweight, lut, bias, self.bits, self.outlier_rowptr, self.outlier_cols, vals)
-        else:
-            y = _lib.lut_linear(x2, self.qweight, lut, bias, self.bits)
-        return y.reshape(out_shape)
+        return self._lut_forward(x2, lut, bias).reshape(out_shape)
+
+
+class _GanqLutLinearFn(torch.autograd.Function):
+    """y = F.linear(x, lut.gather(1, Q) + W_sparse, bias) with HIP gradients for x and lut; x is [M, in_features]"""
+
+    @staticmethod
+    def forward(ctx, x2, lut_in, layer):
+        lut, bias = lut_in, layer.bias
+        if lut.dtype != x2.dtype:
+            lut = lut.to(x2.dtype)
+            bias = None if bias is None else bias.to(x2.dtype)
+        y = layer._lut_forward(x2, lut, bias)
+        ctx.layer = layer
+        ctx.lut_dtype = lut_in.dtype
+        ctx.save_for_backward(lut, x2 if ctx.needs_input_grad[1] else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        layer = ctx.layer
+        lut, x2 = ctx.saved_tensors
+        dy = dy.contiguous()  # (y.sum().backward() hands over a stride-0 gradient)
+        if dy.dtype != lut.dtype:
+            dy = dy.to(lut.dtype)
+        dx = dlut = None
+        if ctx.needs_input_grad[0]:
+            addend = None
+            if layer.outliers:  # dy @ W_sparse in fp32, added before the kernel's one rounding
+                rowptr_t, cols_t, vals_t = layer._outliers_t(dy.dtype)
+                addend = _lib.outlier_matmul(dy, rowptr_t, cols_t, vals_t, layer.in_features)
+            dx = _lib.lut_linear_bwd_input(dy, layer.qweight, lut, layer.bits, addend)
+        if ctx.needs_input_grad[1]:
+            dlut = _lib.lut_linear_bwd_lut(dy, x2, layer.qweight, layer.bits, layer.out_features)
+            if dlut.dtype != ctx.lut_dtype:
+                dlut = dlut.to(ctx.lut_dtype)
+        return dx, dlut, None
 
 
 __all__ = ["GanqHipQuantLinear", "BACKEND_GANQ_HIP"]

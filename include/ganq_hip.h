@@ -217,6 +217,26 @@ int ganq_lut_linear_fwd_outliers(const void* x, const int32_t* qweight, const vo
 int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits, void* Wq_out,
                      void* stream);
 
+/* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
+ * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
+ *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,
+ *              ONE rounding to dtype.  M <= 64: one kernel decodes the packed indices (splits of m summed by a second launch);
+ *              M > 64: Wq^T [n][ceil64(m)] is written to the workspace and multiplied by the forward's dense GEMM.  A layer with
+ *              outliers passes dy @ W_sparse (ganq_outlier_matmul on the transposed CSR) as the addend.  dx 8-byte aligned, addend
+ *              16-byte aligned; dy 16-byte aligned when m is a multiple of 64 and M > 64.
+ *   bwd_lut:   dlut [m,V] fp32 = sum_b sum_j [Q[o][j] == v] * dy[b][o] * x[b][j]   (codes no index uses: exactly 0)
+ *              dy^T and x^T are staged in the workspace with tokens contiguous, the dense GEMM forms dy^T x and sums each product
+ *              into the bin of its code in its epilogue.
+ * Deterministic: bitwise repeatable, no floating-point atomics.  Workspaces need no initialisation, and their sizes depend
+ * only on the arguments (0 for M = 0). */
+size_t ganq_lut_linear_bwd_input_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
+int ganq_lut_linear_bwd_input(const void* dy, const int32_t* qweight, const void* lut, const float* addend, int dtype,
+                              int64_t M, int64_t m, int64_t n, int bits, void* dx, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t ganq_lut_linear_bwd_lut_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
+int ganq_lut_linear_bwd_lut(const void* dy, const void* x, const int32_t* qweight, int dtype, int64_t M, int64_t m,
+                            int64_t n, int bits, float* dlut, void* workspace, size_t workspace_bytes, void* stream);
+
 /* pack Q [m,n] uint8 (original column order) into qweight [n*bits/32, m] int32, and back */
 int ganq_pack_indices(const uint8_t* Q, int64_t m, int64_t n, int bits, int32_t* qweight, void* stream);
 int ganq_unpack_indices(const int32_t* qweight, int64_t m, int64_t n, int bits, uint8_t* Q, void* stream);

@@ -82,6 +82,12 @@ SIGNATURES = {
     "ganq_lut_linear_outliers_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_linear_fwd_outliers": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64,
                                                     _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_linear_lora_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int]),
+    "ganq_lut_linear_fwd_lora": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp, ctypes.c_int, _c_i64, _c_i64,
+                                                _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_linear_lora_outliers_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int]),
+    "ganq_lut_linear_fwd_lora_outliers": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp, ctypes.c_int,
+                                                         _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
     "ganq_lut_linear_bwd_input_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_linear_bwd_input": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp,
                                                  _c_vp, _c_sz, _c_vp]),
@@ -722,6 +728,48 @@ def lut_linear(x, qweight, lut, bias, bits: int, addend=None):
         return y
     _call("ganq_lut_linear_fwd", (x, qweight, lut, bias, y, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias), code, M, m, n, bits,
                                      y.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return y
+
+
+def lut_linear_lora(x, qweight, lut, bias, bits: int, lora_A, lora_B, addend=None, outliers=None):
+    """LUT forward with a low-rank adapter in one library call: y = round(x Wq^T + t lora_B^T (+ addend) (+ bias)) with
+    t = round(x lora_A^T) in x's dtype (fp32 accumulation everywhere, one rounding of y).  x [M,n] fp16/bf16, lora_A [r,n],
+    lora_B [m,r] in x's dtype, r a multiple of 16 in [16, 256]; addend: optional fp32 [M,m].
+    outliers: (rowptr, cols, vals) of a layer with sparse outliers (CSR by output feature, vals in x's dtype) instead of an addend:
+    added inside the decode launch at decode sizes, as the fp32 product of `outlier_matmul` otherwise."""
+    code = _act_dtype(x, "x")
+    if lut.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype) or lora_A.dtype != x.dtype or lora_B.dtype != x.dtype:
+        raise GanqHipError("x, lut, bias, lora_A and lora_B must share one dtype")
+    x, qweight, lut, lora_A, lora_B = x.contiguous(), qweight.contiguous(), lut.contiguous(), lora_A.contiguous(), lora_B.contiguous()
+    M, n = x.shape
+    m = lut.shape[0]
+    r = lora_A.shape[0]
+    if tuple(lora_A.shape) != (r, n) or tuple(lora_B.shape) != (m, r):
+        raise GanqHipError(f"lut_linear_lora: lora_A {tuple(lora_A.shape)} / lora_B {tuple(lora_B.shape)} do not fit x [M,{n}] and {m} out_features")
+    if r < 16 or r > 256 or r % 16:
+        raise GanqHipError(f"lut_linear_lora: rank {r} must be a multiple of 16 in [16, 256]")
+    if addend is not None and (addend.dtype != torch.float32 or tuple(addend.shape) != (M, m) or not addend.is_contiguous()):
+        raise GanqHipError("lut_linear_lora: addend must be a contiguous fp32 [M, out_features] tensor")
+    max_rows = ((1 << 31) - 1) // (2 * max(n, 1)) - 256  # see lut_linear
+    if M > max_rows:
+        step = max(256, max_rows // 256 * 256)
+        return torch.cat([lut_linear_lora(x[i:i + step], qweight, lut, bias, bits, lora_A, lora_B,
+                                          None if addend is None else addend[i:i + step].contiguous(), outliers) for i in range(0, M, step)], dim=0)
+    y = torch.empty((M, m), dtype=x.dtype, device=x.device)
+    if outliers is not None:
+        rowptr, cols, vals = outliers
+        if addend is not None:
+            raise GanqHipError("lut_linear_lora: pass outliers or an addend, not both")
+        if vals.dtype != x.dtype or rowptr.dtype != torch.int32 or cols.dtype != torch.int32 or rowptr.numel() != m + 1:
+            raise GanqHipError("lut_linear_lora: outlier vals in x's dtype, rowptr / cols int32, rowptr of length out_features + 1")
+        ws = _lut_workspace(lib().ganq_lut_linear_lora_outliers_workspace_bytes(M, m, n, bits, r), x.device)
+        _call("ganq_lut_linear_fwd_lora_outliers", (x, qweight, lut, bias, lora_A, lora_B, rowptr, cols, vals, y, ws), x.data_ptr(), qweight.data_ptr(),
+              lut.data_ptr(), _ptr(bias), lora_A.data_ptr(), lora_B.data_ptr(), r, rowptr.data_ptr(), cols.data_ptr() if cols.numel() else None,
+              vals.data_ptr() if vals.numel() else None, code, M, m, n, bits, y.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+        return y
+    ws = _lut_workspace(lib().ganq_lut_linear_lora_workspace_bytes(M, m, n, bits, r), x.device)
+    _call("ganq_lut_linear_fwd_lora", (x, qweight, lut, bias, lora_A, lora_B, addend, y, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(),
+          _ptr(bias), lora_A.data_ptr(), lora_B.data_ptr(), r, _ptr(addend), code, M, m, n, bits, y.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
     return y
 
 

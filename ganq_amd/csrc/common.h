@@ -95,6 +95,14 @@ bool gemm_h16_supported(int64_t M, int64_t N, int64_t K);
 int gemm_h16(const void* x, const void* w, const void* bias, const float* addend, int dtype, int64_t M, int64_t N, int64_t K, void* y,
              hipStream_t stream);
 
+// low-rank adapter of a LUT layer as the forward kernels see it: t = round(x @ lora_A^T) [M, r] and lora_B [m, r], both in the
+// activation dtype and contiguous along r (a multiple of 16); b == nullptr: no adapter
+struct LutLora {
+    const uint16_t* t = nullptr;
+    const uint16_t* b = nullptr;
+    int r = 0;
+};
+
 // the same kernel with the codebook-gradient epilogue (lut_backward.hip): bpart [ceil(N / 256)][M][2^bits] fp32
 int gemm_h16_buckets(const void* xt, const void* wt, const uint32_t* qw, int bits, int dtype, int64_t M, int64_t N, int64_t K, float* bpart,
                      hipStream_t stream);

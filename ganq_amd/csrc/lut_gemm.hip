@@ -45,12 +45,16 @@ constexpr int GPITCH = 64 * GST + 16;  // bytes per LDS row (activations and dec
 // SPLIT: blockIdx.y = ks takes the stages [ks * st_per, (ks + 1) * st_per) of in_features and writes its fp32 partial tile;
 // lut_gemm_reduce_kernel, the next launch on the stream, sums the splits in ks order (deterministic), adds addend / bias and
 // rounds once.  Serves 64 < M <= ~1024, where whole-K tiles would leave CUs idle.
-template <int BITS, bool BF16, bool SPLIT, bool RAGGED>
+// LORA: a low-rank adapter is r more input features whose weights are stored dense: after the stages of in_features (of the
+// first split) come ceil(r / 64) stages whose slab is t = round(x lora_A^T) [M, r] and whose weight tile is lora_B [m, r], copied
+// to LDS as they are (ranks past r as zeros).
+template <int BITS, bool BF16, bool SPLIT, bool RAGGED, bool LORA>
 __global__ __launch_bounds__(256, 2) void lut_gemm_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ qw,
                                                         const uint16_t* __restrict__ lut, const uint16_t* __restrict__ bias,
                                                         const float* __restrict__ addend, int M, int m, int n, int tiles_m,
                                                         int tiles_n, uint16_t* __restrict__ y, int st_per,
-                                                        float* __restrict__ partial) {
+                                                        float* __restrict__ partial, const uint16_t* __restrict__ lt,
+                                                        const uint16_t* __restrict__ lb, int lr) {
     constexpr int V = 1 << BITS;
     constexpr bool STRADDLE = (8 * BITS) % 16 != 0;  // 3-bit: an octet's 24 bits can span two words
     constexpr int TPR = 4 * GST;                     // threads per slab row (16 B each)
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void lut_gemm_kernel(const uint16_t* __rest
     if (st_begin + 1 < nst) gload(st_begin + 1);
     const unsigned char* abase = As + (64 * wv + l31) * GPITCH + 16 * hf;
     const unsigned char* bbase = Bs + l31 * GPITCH + 16 * hf;
-    for (int st = st_begin; st < nst; ++st) {
+    auto compute_stage = [&]() {
         // ---- 2 * GST sub-steps of 16 in_features; the fragments of sub-step u + 1 are read before the matrix instructions of u
         g_u32x4 a_cur[2], b_cur[4];
 #pragma unroll
@@ -212,11 +216,37 @@ __global__ __launch_bounds__(256, 2) void lut_gemm_kernel(const uint16_t* __rest
                 for (int t = 0; t < 4; ++t) b_cur[t] = b_nxt[t];
             }
         }
+    };
+    for (int st = st_begin; st < nst; ++st) {
+        compute_stage();
         if (st + 1 < nst) {
             __syncthreads();  // every wave has read this stage's tiles
             sstore(st + 1);   // the next stage (its loads were issued a stage ago)
             __syncthreads();
             if (st + 2 < nst) gload(st + 2);
+        }
+    }
+    if constexpr (LORA) {
+        if (!SPLIT || blockIdx.y == 0) {  // uniform over the workgroup
+            for (int c0 = 0; c0 < lr; c0 += 32 * GST) {
+                __syncthreads();  // every wave has read the previous stage's tiles
+#pragma unroll
+                for (int i = 0; i < NLD; ++i) {
+                    const int row = r0 + arow0 + RPP * i, c = c0 + 8 * achunk;
+                    g_u32x4 v = {0u, 0u, 0u, 0u};
+                    if (row < M && c < lr) v = *reinterpret_cast<const g_u32x4*>(lt + (int64_t)row * lr + c);
+                    *reinterpret_cast<g_u32x4*>(As + (arow0 + RPP * i) * GPITCH + 16 * achunk) = v;
+                }
+#pragma unroll
+                for (int j = 0; j < 2 * GST; ++j) {
+                    const int ch = dq0 + 2 * j, c = c0 + 8 * ch;
+                    g_u32x4 v = {0u, 0u, 0u, 0u};
+                    if (c < lr) v = *reinterpret_cast<const g_u32x4*>(lb + (int64_t)dcol * lr + c);
+                    *reinterpret_cast<g_u32x4*>(Bs + dfeat * GPITCH + 16 * ch) = v;
+                }
+                __syncthreads();
+                compute_stage();
+            }
         }
     }
 
@@ -547,20 +577,24 @@ GemmPlan lut_gemm_plan(int64_t M, int64_t m, int64_t n) {
 
 template <int BITS>
 static int launch_gemm_bits(const void* x, const uint32_t* qw, const void* lut, const void* bias, const float* addend, int dtype, int M,
-                            int m, int n, void* y, const GemmPlan& p, float* partial, hipStream_t stream) {
+                            int m, int n, void* y, const GemmPlan& p, float* partial, hipStream_t stream, const LutLora& lora) {
     const uint16_t* xp = static_cast<const uint16_t*>(x);
     const uint16_t* lp = static_cast<const uint16_t*>(lut);
     const uint16_t* bp = static_cast<const uint16_t*>(bias);
     uint16_t* yp = static_cast<uint16_t*>(y);
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.KS);
-#define GANQ_GEMM_LAUNCH(BF, SP)                                                                                                        \
-    do {                                                                                                                                \
-        if ((n & 63) != 0)                                                                                                              \
-            hipLaunchKernelGGL((lut_gemm_kernel<BITS, BF, SP, true>), grid, dim3(256), 0, stream, xp, qw, lp, bp, addend, M, m, n,      \
-                               p.tiles_m, p.tiles_n, yp, p.st_per, partial);                                                            \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((lut_gemm_kernel<BITS, BF, SP, false>), grid, dim3(256), 0, stream, xp, qw, lp, bp, addend, M, m, n,     \
-                               p.tiles_m, p.tiles_n, yp, p.st_per, partial);                                                            \
+#define GANQ_GEMM_LAUNCH1(BF, SP, RG, LO)                                                                                               \
+    hipLaunchKernelGGL((lut_gemm_kernel<BITS, BF, SP, RG, LO>), grid, dim3(256), 0, stream, xp, qw, lp, bp, addend, M, m, n, p.tiles_m, \
+                       p.tiles_n, yp, p.st_per, partial, lora.t, lora.b, lora.r)
+#define GANQ_GEMM_LAUNCH(BF, SP)                                       \
+    do {                                                               \
+        if (lora.b) {                                                  \
+            if ((n & 63) != 0) GANQ_GEMM_LAUNCH1(BF, SP, true, true);  \
+            else GANQ_GEMM_LAUNCH1(BF, SP, false, true);               \
+        } else {                                                       \
+            if ((n & 63) != 0) GANQ_GEMM_LAUNCH1(BF, SP, true, false); \
+            else GANQ_GEMM_LAUNCH1(BF, SP, false, false);              \
+        }                                                              \
     } while (0)
     const int pipe_opt = (int)opt_get(OPT_LUT_GEMM_PIPE);
     // measured (4-bit, fp16, both kernels with buffer loads): about one tile per CU (4096 x 4096, M = 2048: 256 tiles) 87 us
@@ -574,7 +608,8 @@ static int launch_gemm_bits(const void* x, const uint32_t* qw, const void* lut, 
     if (!fits32)
         return fail(-1, "ganq_lut_linear_fwd: x (%lld x %lld) or qweight beyond the 2 GB window of the GEMM's buffer loads: split the "
                         "rows of x over several calls", (long long)M, (long long)n);
-    const bool pipe = p.KS == 1 && (pipe_opt >= 0 ? pipe_opt != 0 : pipe_by_shape);
+    // (a layer with an adapter takes the two-workgroups-per-CU kernel: the pipelined one has no adapter stages)
+    const bool pipe = !lora.b && p.KS == 1 && (pipe_opt >= 0 ? pipe_opt != 0 : pipe_by_shape);
     if (pipe) {
         const bool ragged = (n & 63) != 0;
 #define GANQ_PIPE_LAUNCH(BF, RG)                                                                                                   \
@@ -607,6 +642,7 @@ static int launch_gemm_bits(const void* x, const uint32_t* qw, const void* lut, 
         else GANQ_GEMM_LAUNCH(false, false);
     }
 #undef GANQ_GEMM_LAUNCH
+#undef GANQ_GEMM_LAUNCH1
     GANQ_LAUNCH_CHECK();
     return 0;
 }
@@ -615,14 +651,14 @@ static int launch_gemm_bits(const void* x, const uint32_t* qw, const void* lut, 
 size_t lut_gemm_workspace_bytes(int64_t M, int64_t m, int64_t n) { return lut_gemm_plan(M, m, n).partial_bytes; }
 
 int lut_gemm(const void* x, const uint32_t* qw, const void* lut, const void* bias, const float* addend, int dtype, int64_t M,
-             int64_t m, int64_t n, int bits, void* y, float* partial, size_t partial_bytes, hipStream_t stream) {
+             int64_t m, int64_t n, int bits, void* y, float* partial, size_t partial_bytes, hipStream_t stream, const LutLora& lora) {
     if (M > INT32_MAX / 2) return fail(-1, "ganq_lut_linear_fwd: M too large");
     const GemmPlan p = lut_gemm_plan(M, m, n);
     if (p.KS > 1 && (!partial || partial_bytes < p.partial_bytes))
         return fail(-4, "ganq_lut_linear_fwd: workspace %zu B < required %zu B of partial tiles", partial_bytes, p.partial_bytes);
-    if (bits == 2) return launch_gemm_bits<2>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream);
-    if (bits == 3) return launch_gemm_bits<3>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream);
-    return launch_gemm_bits<4>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream);
+    if (bits == 2) return launch_gemm_bits<2>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream, lora);
+    if (bits == 3) return launch_gemm_bits<3>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream, lora);
+    return launch_gemm_bits<4>(x, qw, lut, bias, addend, dtype, (int)M, (int)m, (int)n, y, p, partial, stream, lora);
 }
 
 }  // namespace ganq

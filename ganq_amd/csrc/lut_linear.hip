@@ -58,13 +58,16 @@ __device__ __forceinline__ uint32_t lds_pair(uint32_t addr_lo, uint32_t addr_hi)
 // partial tiles meet in memory (ticket).  INWG = true: the NW waves share ONE set of 32 features and split
 // in_features among themselves; the partial tiles meet in LDS -- no second memory round trip, which at decode sizes
 // is what the kernel's time is made of.
-template <int BITS, int RT, bool BF16, int NW, bool INWG>
+// LORA: the launch also adds the low-rank adapter, (t = x lora_A^T) lora_B^T, as r / 32 more matrix-core steps whose A operand is
+// t and whose B operand is lora_B read directly (no table lookup); they go with the first split of in_features.
+template <int BITS, int RT, bool BF16, int NW, bool INWG, bool LORA>
 __global__ __launch_bounds__(NW * 64) void lut_mfma_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ qw,
                                                           const uint16_t* __restrict__ lut, const uint16_t* __restrict__ bias,
                                                           const float* __restrict__ addend, int M, int m, int n, int kb_per_wg,
                                                           int KS,
                                                           float* __restrict__ partial, int* __restrict__ counters,
-                                                          uint16_t* __restrict__ y) {
+                                                          uint16_t* __restrict__ y, const uint16_t* __restrict__ lt,
+                                                          const uint16_t* __restrict__ lb, int lr) {
     constexpr int V = 1 << BITS;
     constexpr int KC = 4;  // groups in flight per wave (loads issued one chunk ahead)
     constexpr bool STRADDLE = (8 * BITS) % 16 != 0;  // 3-bit: a lane's 24 bits can span two words
@@ -179,6 +182,37 @@ __global__ __launch_bounds__(NW * 64) void lut_mfma_kernel(const uint16_t* __res
         if (kb0 + KC < kb_end) {
             if (kb0 + 2 * KC < kb_end) issue(0, kb0 + 2 * KC);
             consume(1);
+        }
+    }
+
+    if constexpr (LORA) {
+        if (INWG ? wv == 0 : ks == 0) {  // r is a multiple of 16: an octet of 8 ranks is inside r or past it as a whole
+            for (int kk = 0; kk < lr; kk += 32) {
+                const int k0 = kk + 8 * q;
+                u32x4 bb[2], aa[RT];
+                bb[0] = bb[1] = u32x4{0u, 0u, 0u, 0u};
+                if (k0 < lr) {
+                    bb[0] = *reinterpret_cast<const u32x4*>(lb + (int64_t)oc0 * lr + k0);
+                    bb[1] = *reinterpret_cast<const u32x4*>(lb + (int64_t)oc1 * lr + k0);
+                }
+#pragma unroll
+                for (int r = 0; r < RT; ++r) {
+                    const int xr = 16 * r + col;
+                    aa[r] = u32x4{0u, 0u, 0u, 0u};
+                    if (k0 < lr && xr < M) aa[r] = *reinterpret_cast<const u32x4*>(lt + (int64_t)xr * lr + k0);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) {
+                        if (BF16)
+                            acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, aa[r]),
+                                                                                __builtin_bit_cast(bf16x8, bb[t]), acc[t][r], 0, 0, 0);
+                        else
+                            acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, aa[r]),
+                                                                               __builtin_bit_cast(f16x8, bb[t]), acc[t][r], 0, 0, 0);
+                    }
+            }
         }
     }
 
@@ -302,14 +336,21 @@ __global__ __launch_bounds__(NW * 64) void lut_mfma_kernel(const uint16_t* __res
 // in_features once more, ACROSS workgroups.  Wave 0 of each workgroup stores the workgroup's tile as fp32 (device-scope
 // stores, like lut_mfma_kernel), takes a ticket on the feature block's counter, and the last one to arrive sums the
 // partial tiles in split order (deterministic), adds addend / bias and writes y; it leaves the counter 0.
-template <int BITS, int RT, bool BF16, int NT, int KC, bool SPLIT>
-__global__ __launch_bounds__(1024, (RT == 1 && BITS != 3) ? 8 : 4) void lut_decode_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ qw,
+//
+// LORA: the low-rank adapter (t = x lora_A^T, formed by lora_t_kernel; lora_B [m, r]) is r / 32 <= 8 further matrix-core steps,
+// dealt one per wave like the outliers: wave w loads the w-th 32 ranks of t (A operand) and of lora_B (B operand, no lookup)
+// and adds the step to its accumulators before the reduction -- still one rounding of y.  The two operands are loaded with the
+// wave's first weight words where the register budget allows (LPRE; the 16-feature variant then runs at 128 registers, which
+// costs nothing: it has one workgroup per CU anyway), and after the weight loop in the 64-register variants.
+template <int BITS, int RT, bool BF16, int NT, int KC, bool SPLIT, bool LORA>
+__global__ __launch_bounds__(1024, (RT == 1 && BITS != 3 && !(LORA && NT == 1)) ? 8 : 4) void lut_decode_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ qw,
                                                           const uint16_t* __restrict__ lut, const uint16_t* __restrict__ bias,
                                                           const float* __restrict__ addend, const int32_t* __restrict__ rowptr,
                                                           const int32_t* __restrict__ ocols, const uint16_t* __restrict__ ovals,
                                                           int M, int m, int n, int kb_per_wave, int kb_per_wg, int KS,
                                                           float* __restrict__ partial, int* __restrict__ counters,
-                                                          uint16_t* __restrict__ y) {
+                                                          uint16_t* __restrict__ y, const uint16_t* __restrict__ lt,
+                                                          const uint16_t* __restrict__ lb, int lr) {
     constexpr int V = 1 << BITS;
     constexpr int NW = 16;
     constexpr bool STRADDLE = (8 * BITS) % 16 != 0;  // 3-bit: a lane's 24 bits can span two words
@@ -389,6 +430,26 @@ __global__ __launch_bounds__(1024, (RT == 1 && BITS != 3) ? 8 : 4) void lut_deco
         for (int r = 0; r < RT; ++r) acc[t][r] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (kb_begin < kb_end) issue(kb_begin);  // everything this wave needs (n <= 32 * 16 * KC) is in flight from here on
+    // adapter: this wave's step (r <= 256: at most 8 steps for 16 waves), with the first split; r is a multiple of 16, so an
+    // octet of 8 ranks lies inside r or past it as a whole
+    constexpr bool LPRE = !(RT == 1 && BITS != 3) || NT == 1;
+    u32x4 la[LORA ? RT : 1], lbv[LORA ? NT : 1];
+    auto lora_load = [&]() {
+        const int k0 = 32 * wv + 8 * q;
+        const bool kok = ks == 0 && k0 < lr;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            lbv[t] = u32x4{0u, 0u, 0u, 0u};
+            if (kok) lbv[t] = *reinterpret_cast<const u32x4*>(lb + (int64_t)oc[t] * lr + k0);
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const int xr = 16 * r + col;
+            la[r] = u32x4{0u, 0u, 0u, 0u};
+            if (kok && xr < M) la[r] = *reinterpret_cast<const u32x4*>(lt + (int64_t)xr * lr + k0);
+        }
+    };
+    if constexpr (LORA && LPRE) lora_load();
     {   // wave t fetches the V entries of every lane's feature of tile t and fills that tile's table
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -452,6 +513,23 @@ __global__ __launch_bounds__(1024, (RT == 1 && BITS != 3) ? 8 : 4) void lut_deco
     for (int kb0 = kb_begin; kb0 < kb_end; kb0 += KC) {
         if (kb0 != kb_begin) issue(kb0);
         consume();
+    }
+
+    if constexpr (LORA) {
+        if constexpr (!LPRE) lora_load();
+        if (ks == 0 && 32 * wv < lr) {  // wave-uniform
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < RT; ++r) {
+                    if (BF16)
+                        acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, la[r]),
+                                                                            __builtin_bit_cast(bf16x8, lbv[t]), acc[t][r], 0, 0, 0);
+                    else
+                        acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, la[r]),
+                                                                           __builtin_bit_cast(f16x8, lbv[t]), acc[t][r], 0, 0, 0);
+                }
+        }
     }
 
     // sparse part: D[row][feature] += x[row][c_j] * v_j over this wave's entries of the feature (fp32)
@@ -652,6 +730,176 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict_
     Q[i] = (uint8_t)(v & ((1u << bits) - 1u));
 }
 
+// t[M, r] = round(x[M, n] @ lora_A[r, n]^T): the thin first product of a low-rank adapter (a 256-wide tile of the dense GEMM is
+// mostly empty at N = r: 50 us for 512 x 4096 x 32 against the 42 us of the whole LUT forward).  One workgroup = 16 RT rows of x
+// and a range of 32-column groups (blockIdx.y); v_mfma_f32_16x16x32, x the A operand, lora_A the B operand (16-byte loads both).
+//   WR = false (up to 64 rows, the decode regime): 16 ranks per workgroup, its NWV waves take the column groups in turn and
+//     their tiles meet in LDS in wave order.
+//   WR = true (row blocks of 64 for M > 64): every wave owns 16 ranks of its own (NWV x 16 per workgroup, x shared through L1).
+// With KS > 1 the fp32 tiles go to memory (device-scope stores) and the last workgroup to take a ticket on the tile's counter sums
+// the KS tiles in split order, rounds once and leaves the counter 0 -- the exchange of lut_decode_kernel.
+template <bool BF16, int RT, int NWV, bool WR>
+__global__ __launch_bounds__(NWV * 64) void lora_t_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ A, int M, int n, int r,
+                                                          int kb_per_wg, int KS, float* __restrict__ partial, int* __restrict__ counters,
+                                                          uint16_t* __restrict__ t) {
+    __shared__ float red[WR ? 1 : NWV - 1][RT][4][64];
+    __shared__ int s_ticket;
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, q = lane >> 4;
+    const int j0 = 16 * (WR ? (int)blockIdx.x * NWV + wv : (int)blockIdx.x), ks = blockIdx.y, r0 = blockIdx.z * (16 * RT);
+    const bool active = j0 < r;  // (WR: a wave past the last 16 ranks only keeps the barriers company)
+    const int nkb = n >> 5;
+    const int kb_begin = min(nkb, ks * kb_per_wg), kb_end = min(nkb, kb_begin + kb_per_wg);
+    const uint16_t* ap = A + (int64_t)(active ? j0 + col : 0) * n + 8 * q;  // r is a multiple of 16: rank j0 + col exists
+    f32x4 acc[RT];
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr) acc[rr] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (active) {
+#pragma unroll 4
+        for (int kb = kb_begin + (WR ? 0 : wv); kb < kb_end; kb += (WR ? 1 : NWV)) {
+            const u32x4 b = *reinterpret_cast<const u32x4*>(ap + 32 * kb);
+            u32x4 a[RT];
+#pragma unroll
+            for (int rr = 0; rr < RT; ++rr) {
+                const int xr = r0 + 16 * rr + col;
+                a[rr] = u32x4{0u, 0u, 0u, 0u};
+                if (xr < M) a[rr] = *reinterpret_cast<const u32x4*>(x + (int64_t)xr * n + 32 * kb + 8 * q);
+            }
+#pragma unroll
+            for (int rr = 0; rr < RT; ++rr) {
+                if (BF16)
+                    acc[rr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[rr]), __builtin_bit_cast(bf16x8, b), acc[rr], 0, 0, 0);
+                else
+                    acc[rr] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[rr]), __builtin_bit_cast(f16x8, b), acc[rr], 0, 0, 0);
+            }
+        }
+    }
+    float v[RT][4];
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[rr][i] = acc[rr][i];
+    if constexpr (!WR) {
+        if (wv > 0) {
+#pragma unroll
+            for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) red[wv - 1][rr][i][lane] = acc[rr][i];
+        }
+        __syncthreads();
+        if (wv != 0) return;
+#pragma unroll
+        for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int w2 = 0; w2 < NWV - 1; ++w2) v[rr][i] += red[w2][rr][i][lane];  // fixed order
+    }
+    auto put = [&](float val, int row) {
+        t[(int64_t)row * r + j0 + col] = BF16 ? __builtin_bit_cast(uint16_t, (__bf16)val) : __builtin_bit_cast(uint16_t, (_Float16)val);
+    };
+    if (KS == 1) {
+#pragma unroll
+        for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = r0 + 16 * rr + 4 * q + i;
+                if (active && row < M) put(v[rr][i], row);
+            }
+        return;
+    }
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = r0 + 16 * rr + 4 * q + i;
+            if (active && row < M)
+                __hip_atomic_store(&partial[((int64_t)ks * M + row) * r + j0 + col], v[rr][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    // device-scope stores are visible to every XCD once vmcnt reaches 0 (no cache walk), then the ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int cidx = blockIdx.z * gridDim.x + blockIdx.x;
+    int ticket = 0;
+    if constexpr (WR) {
+        __syncthreads();
+        if (tid == 0) s_ticket = __hip_atomic_fetch_add(&counters[cidx], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        ticket = s_ticket;
+    } else {  // only wave 0 is left
+        if (lane == 0) ticket = __hip_atomic_fetch_add(&counters[cidx], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ticket = __builtin_amdgcn_readfirstlane(ticket);
+    }
+    if (ticket != KS - 1) return;
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[rr][i] = 0.f;
+    for (int k2 = 0; k2 < KS; ++k2) {
+        float pv[RT][4];
+#pragma unroll
+        for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = r0 + 16 * rr + 4 * q + i;
+                pv[rr][i] = (active && row < M)
+                                ? __hip_atomic_load(&partial[((int64_t)k2 * M + row) * r + j0 + col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                : 0.f;
+            }
+#pragma unroll
+        for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[rr][i] += pv[rr][i];
+    }
+#pragma unroll
+    for (int rr = 0; rr < RT; ++rr)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = r0 + 16 * rr + 4 * q + i;
+            if (active && row < M) put(v[rr][i], row);
+        }
+    if (tid == 0) __hip_atomic_store(&counters[cidx], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // clean for the next call
+}
+
+// P[M, m] fp32 = t[M, r] @ lora_B[m, r]^T (+ addend): the adapter's second product on its own, for the shapes whose LUT forward takes
+// the dense path (gemm_h16.hip has no second K segment): it goes in as that call's fp32 addend, like the sparse-outlier product.
+// One workgroup = 64 rows x 64 features, wave w its rows 16 w .. 16 w + 15; K = r in steps of 32 on v_mfma_f32_16x16x32, ranks past
+// r as zeros.  Bound by the M x m x 4 bytes it writes.
+template <bool BF16>
+__global__ __launch_bounds__(256) void lora_addend_kernel(const uint16_t* __restrict__ t, const uint16_t* __restrict__ B,
+                                                          const float* __restrict__ addend, int M, int m, int r, float* __restrict__ P) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, q = lane >> 4;
+    const int o0 = blockIdx.x * 64, r0 = blockIdx.y * 64 + 16 * wv;
+    const int xr = r0 + col;
+    f32x4 acc[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kk = 0; kk < r; kk += 32) {
+        const int k0 = kk + 8 * q;  // r is a multiple of 16: an octet lies inside r or past it as a whole
+        u32x4 a = {0u, 0u, 0u, 0u};
+        if (k0 < r && xr < M) a = *reinterpret_cast<const u32x4*>(t + (int64_t)xr * r + k0);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            u32x4 b = {0u, 0u, 0u, 0u};
+            if (k0 < r) b = *reinterpret_cast<const u32x4*>(B + (int64_t)min(o0 + 16 * f + col, m - 1) * r + k0);
+            if (BF16)
+                acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc[f], 0, 0, 0);
+            else
+                acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc[f], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = r0 + 4 * q + i, o = o0 + 16 * f + col;
+            if (row < M && o < m) {
+                const int64_t idx = (int64_t)row * m + o;
+                P[idx] = acc[f][i] + (addend ? addend[idx] : 0.f);
+            }
+        }
+}
+
 // The ticket counters occupy a FIXED region at the head of the workspace (one int per block of output features, up to
 // 16384 blocks), the partial tiles start behind it: one workspace serves layers of any shape in turn, and the floats
 // a smaller layer left in the partial-tile region can never be read as counters by a larger one.
@@ -714,7 +962,8 @@ static LutPlan lut_plan(int64_t M, int64_t m, int64_t n, int bits) {
 
 // lut_gemm.hip: the fused LUT-dequant GEMM that serves M > LUT_MAX_M (prefill)
 int lut_gemm(const void* x, const uint32_t* qw, const void* lut, const void* bias, const float* addend, int dtype, int64_t M,
-             int64_t m, int64_t n, int bits, void* y, float* partial, size_t partial_bytes, hipStream_t stream);
+             int64_t m, int64_t n, int bits, void* y, float* partial, size_t partial_bytes, hipStream_t stream,
+             const LutLora& lora = LutLora());
 size_t lut_gemm_workspace_bytes(int64_t M, int64_t m, int64_t n);
 
 // Prefill with many rows: dequantise the layer ONCE into the workspace and run the dense GEMM (gemm_h16.hip) -- every 256-row
@@ -759,28 +1008,37 @@ struct LutCsr {  // sparse outliers of the layer (device pointers; rowptr == nul
     const uint16_t* vals = nullptr;
 };
 
-template <int BITS, int RT, bool BF16, int NT>
-static void launch_decode(const uint16_t* xp, const uint32_t* qw, const uint16_t* lp, const uint16_t* bp, const float* addend,
-                          const LutCsr& csr, int M, int m, int n, const LutPlan& p, float* partial, int* counters, uint16_t* yp,
-                          hipStream_t stream) {
+template <int BITS, int RT, bool BF16, int NT, bool LORA>
+static void launch_decode_lora(const uint16_t* xp, const uint32_t* qw, const uint16_t* lp, const uint16_t* bp, const float* addend,
+                               const LutCsr& csr, int M, int m, int n, const LutPlan& p, float* partial, int* counters, uint16_t* yp,
+                               hipStream_t stream, const LutLora& lora) {
     // groups of 32 columns a wave has in flight.  16 features per workgroup: 8 (n = 4096: all of its share).  32 features:
     // 4, which fits 64 registers, so two workgroups share a CU and the 448 workgroups of m = 14336 are resident in one
     // generation (measured cold, M = 1, 14336 x 4096: 14.6 -> 10.9 us; a double-buffered 4 + 4 loop for 16 features was
     // slower at 4096 x 4096, 6.6 vs 5.7 us)
     constexpr int KC = (RT == 1 && NT == 1) ? 8 : 4;
     if (p.KS > 1)
-        hipLaunchKernelGGL((lut_decode_kernel<BITS, RT, BF16, NT, KC, true>), dim3((unsigned)p.ob, (unsigned)p.KS), dim3(1024), 0, stream,
+        hipLaunchKernelGGL((lut_decode_kernel<BITS, RT, BF16, NT, KC, true, LORA>), dim3((unsigned)p.ob, (unsigned)p.KS), dim3(1024), 0, stream,
                            xp, qw, lp, bp, addend, csr.rowptr, csr.cols, csr.vals, M, m, n, p.kb_per_wave, p.kb_per_wg, p.KS, partial,
-                           counters, yp);
+                           counters, yp, lora.t, lora.b, lora.r);
     else
-        hipLaunchKernelGGL((lut_decode_kernel<BITS, RT, BF16, NT, KC, false>), dim3((unsigned)p.ob), dim3(1024), 0, stream, xp, qw, lp, bp,
-                           addend, csr.rowptr, csr.cols, csr.vals, M, m, n, p.kb_per_wave, p.kb_per_wg, 1, partial, counters, yp);
+        hipLaunchKernelGGL((lut_decode_kernel<BITS, RT, BF16, NT, KC, false, LORA>), dim3((unsigned)p.ob), dim3(1024), 0, stream, xp, qw, lp, bp,
+                           addend, csr.rowptr, csr.cols, csr.vals, M, m, n, p.kb_per_wave, p.kb_per_wg, 1, partial, counters, yp, lora.t,
+                           lora.b, lora.r);
+}
+
+template <int BITS, int RT, bool BF16, int NT>
+static void launch_decode(const uint16_t* xp, const uint32_t* qw, const uint16_t* lp, const uint16_t* bp, const float* addend,
+                          const LutCsr& csr, int M, int m, int n, const LutPlan& p, float* partial, int* counters, uint16_t* yp,
+                          hipStream_t stream, const LutLora& lora) {
+    if (lora.b) launch_decode_lora<BITS, RT, BF16, NT, true>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
+    else launch_decode_lora<BITS, RT, BF16, NT, false>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
 }
 
 template <int BITS, int RT>
 static int launch_lut_rt(const void* x, const uint32_t* qw, const void* lut, const void* bias, const float* addend, const LutCsr& csr,
                          int dtype, int M, int m, int n,
-                         const LutPlan& p, float* partial, int* counters, void* y, hipStream_t stream) {
+                         const LutPlan& p, float* partial, int* counters, void* y, hipStream_t stream, const LutLora& lora) {
     const dim3 grid((unsigned)p.ob, (unsigned)p.KS);
     const uint16_t* xp = static_cast<const uint16_t*>(x);
     const uint16_t* lp = static_cast<const uint16_t*>(lut);
@@ -792,25 +1050,30 @@ static int launch_lut_rt(const void* x, const uint32_t* qw, const void* lut, con
             // buffer of two row tiles do not fit the LDS); the plan knows
             if constexpr (RT == 1) {
                 if (p.nt == 2) {
-                    if (dtype == 1) launch_decode<BITS, RT, true, 2>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream);
-                    else launch_decode<BITS, RT, false, 2>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream);
+                    if (dtype == 1) launch_decode<BITS, RT, true, 2>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
+                    else launch_decode<BITS, RT, false, 2>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
                     GANQ_LAUNCH_CHECK();
                     return 0;
                 }
             }
-            if (dtype == 1) launch_decode<BITS, RT, true, 1>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream);
-            else launch_decode<BITS, RT, false, 1>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream);
+            if (dtype == 1) launch_decode<BITS, RT, true, 1>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
+            else launch_decode<BITS, RT, false, 1>(xp, qw, lp, bp, addend, csr, M, m, n, p, partial, counters, yp, stream, lora);
             GANQ_LAUNCH_CHECK();
             return 0;
         }
     }
     if (csr.rowptr) return fail(-2, "ganq_lut_linear_fwd: the fused outlier path serves the decode kernel only");
-    if (dtype == 1)
-        hipLaunchKernelGGL((lut_mfma_kernel<BITS, RT, true, LW, false>), grid, dim3(LW * 64), 0, stream, xp, qw, lp, bp, addend, M, m, n,
-                           p.kb_per_wg, p.KS, partial, counters, yp);
-    else
-        hipLaunchKernelGGL((lut_mfma_kernel<BITS, RT, false, LW, false>), grid, dim3(LW * 64), 0, stream, xp, qw, lp, bp, addend, M, m, n,
-                           p.kb_per_wg, p.KS, partial, counters, yp);
+#define GANQ_MFMA_LAUNCH(BF, LO)                                                                                                     \
+    hipLaunchKernelGGL((lut_mfma_kernel<BITS, RT, BF, LW, false, LO>), grid, dim3(LW * 64), 0, stream, xp, qw, lp, bp, addend, M, m, n, \
+                       p.kb_per_wg, p.KS, partial, counters, yp, lora.t, lora.b, lora.r)
+    if (lora.b) {
+        if (dtype == 1) GANQ_MFMA_LAUNCH(true, true);
+        else GANQ_MFMA_LAUNCH(false, true);
+    } else {
+        if (dtype == 1) GANQ_MFMA_LAUNCH(true, false);
+        else GANQ_MFMA_LAUNCH(false, false);
+    }
+#undef GANQ_MFMA_LAUNCH
     GANQ_LAUNCH_CHECK();
     return 0;
 }
@@ -818,10 +1081,10 @@ static int launch_lut_rt(const void* x, const uint32_t* qw, const void* lut, con
 template <int BITS>
 static int launch_lut(const void* x, const uint32_t* qw, const void* lut, const void* bias, const float* addend, const LutCsr& csr,
                       int dtype, int M, int m, int n,
-                      const LutPlan& p, float* partial, int* counters, void* y, hipStream_t stream) {
-    if (M <= 16) return launch_lut_rt<BITS, 1>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream);
-    if (M <= 32) return launch_lut_rt<BITS, 2>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream);
-    return launch_lut_rt<BITS, 4>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream);
+                      const LutPlan& p, float* partial, int* counters, void* y, hipStream_t stream, const LutLora& lora) {
+    if (M <= 16) return launch_lut_rt<BITS, 1>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream, lora);
+    if (M <= 32) return launch_lut_rt<BITS, 2>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream, lora);
+    return launch_lut_rt<BITS, 4>(x, qw, lut, bias, addend, csr, dtype, M, m, n, p, partial, counters, y, stream, lora);
 }
 
 static int check_lut_args(const char* who, int dtype, int64_t m, int64_t n, int bits) {
@@ -834,7 +1097,7 @@ static int check_lut_args(const char* who, int dtype, int64_t m, int64_t n, int 
 
 static int lut_linear_fwd(const void* x, const int32_t* qweight, const void* lut, const void* bias, const float* addend, int dtype,
                           int64_t M, int64_t m, int64_t n, int bits, void* y, void* workspace, size_t workspace_bytes,
-                          void* stream_, const LutCsr& csr = LutCsr()) {
+                          void* stream_, const LutCsr& csr = LutCsr(), const LutLora& lora = LutLora()) {
     if (M < 0 || m < 0 || n < 0) return fail(-1, "ganq_lut_linear_fwd: negative shape");
     if (M == 0 || m == 0) return 0;
     int rc = check_lut_args("ganq_lut_linear_fwd", dtype, m, n, bits);
@@ -850,7 +1113,8 @@ static int lut_linear_fwd(const void* x, const int32_t* qweight, const void* lut
         if (!workspace || workspace_bytes < LUT_COUNTER_BYTES)
             return fail(-4, "ganq_lut_linear_fwd: workspace %zu B < required %zu B", workspace_bytes, LUT_COUNTER_BYTES);
         ProfScope gprof(KID_LUT_GEMM, gstream);
-        if (lut_dense_path(M, m, n)) {
+        // (adapter steps handed over: the caller chose the fused kernel, whose loop over in_features takes the ranks as further steps)
+        if (!lora.b && lut_dense_path(M, m, n)) {
             const size_t need = LUT_COUNTER_BYTES + align_up((size_t)m * (size_t)n * 2, 256);
             if (workspace_bytes < need) return fail(-4, "ganq_lut_linear_fwd: workspace %zu B < required %zu B", workspace_bytes, need);
             uint16_t* Wd = reinterpret_cast<uint16_t*>(static_cast<char*>(workspace) + LUT_COUNTER_BYTES);
@@ -868,7 +1132,7 @@ static int lut_linear_fwd(const void* x, const int32_t* qweight, const void* lut
         }
         return lut_gemm(x, reinterpret_cast<const uint32_t*>(qweight), lut, bias, addend, dtype, M, m, n, bits, y,
                         reinterpret_cast<float*>(static_cast<char*>(workspace) + LUT_COUNTER_BYTES), workspace_bytes - LUT_COUNTER_BYTES,
-                        gstream);
+                        gstream, lora);
     }
     const LutPlan p = lut_plan(M, m, n, bits);
     if ((size_t)p.ob * sizeof(int) > LUT_COUNTER_BYTES)
@@ -881,9 +1145,9 @@ static int lut_linear_fwd(const void* x, const int32_t* qweight, const void* lut
     float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.counter_bytes);
     const uint32_t* qw = reinterpret_cast<const uint32_t*>(qweight);
     ProfScope prof(KID_LUT_GEMV, stream);
-    if (bits == 2) rc = launch_lut<2>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream);
-    else if (bits == 3) rc = launch_lut<3>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream);
-    else rc = launch_lut<4>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream);
+    if (bits == 2) rc = launch_lut<2>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream, lora);
+    else if (bits == 3) rc = launch_lut<3>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream, lora);
+    else rc = launch_lut<4>(x, qw, lut, bias, addend, csr, dtype, (int)M, (int)m, (int)n, p, partial, counters, y, stream, lora);
     return rc;
 }
 
@@ -933,6 +1197,188 @@ extern "C" int ganq_lut_linear_fwd_outliers(const void* x, const int32_t* qweigh
     int rc = ganq_outlier_matmul(x, dtype, M, m, n, rowptr, cols, vals, addend, stream_);
     if (rc) return rc;
     return lut_linear_fwd(x, qweight, lut, bias, addend, dtype, M, m, n, bits, y, workspace, base, stream_);
+}
+
+// ---- LUT forward of a layer with a low-rank adapter: y = round(x Wq^T + (x lora_A^T) lora_B^T (+ addend) (+ bias)).
+// Two steps on the stream: t = round(x lora_A^T) [M, r] into the workspace (lora_t_kernel), then the LUT kernel of the regime
+// with r / 32 further matrix-core steps on (t, lora_B).  Where the plain forward takes the dense path and in_features >= 8192 there are
+// three: t, P = t lora_B^T as fp32 (lora_addend_kernel), and the plain call with P as its addend.
+// Workspace: [the LUT kernels' own] [t] [t split tiles] [P, dense regime only].  The tickets of the t kernel are the last
+// LORA_T_COUNTERS ints of the fixed counter region at the head of the workspace (the LUT kernels use one per feature block from
+// its start), so they too can never be floats another shape left behind.
+constexpr int LORA_T_COUNTERS = 1024;
+constexpr int LORA_T_COUNTER0 = (int)(LUT_COUNTER_BYTES / sizeof(int)) - LORA_T_COUNTERS;
+constexpr int LORA_T_WAVES = 16;   // decode regime: waves per workgroup, all on the same 16 ranks (8 with four row tiles: registers)
+constexpr int LORA_T_RWAVES = 4;   // row blocks: waves per workgroup, 16 ranks each
+struct LoraTPlan {
+    int rt, zb, xt, KS, kb_per_wg;
+    bool wr;  // row blocks of 64 (M > 64)
+    size_t t_bytes, partial_bytes;
+};
+// M > 64 where the plain forward takes the dense path AND in_features is long: the adapter's second product becomes the fp32 addend
+// of that path.  The round trip of P costs 8 M m bytes whatever n is, the fused kernel's handicap against the dense path grows with
+// n.  Measured (4-bit fp16, us, fused kernel with adapter stages / this way): 4096 x 14336 M = 2048 r = 32 393 / 308, M = 4096
+// r = 128 669 / 597; 14336 x 4096 M = 2048 r = 128 331 / 396, M = 4096 r = 32 560 / 617; 4096 x 4096 within 10 % either way.
+constexpr int64_t LORA_DENSE_MIN_N = 8192;
+static bool lut_lora_dense(int64_t M, int64_t m, int64_t n) { return M > LUT_MAX_M && n >= LORA_DENSE_MIN_N && lut_dense_path(M, m, n); }
+static size_t lut_lora_base_bytes(int64_t M, int64_t m, int64_t n, int bits) {
+    if (lut_lora_dense(M, m, n)) return align_up(ganq_lut_linear_workspace_bytes(M, m, n, bits), 256);
+    if (M > LUT_MAX_M) return align_up(LUT_COUNTER_BYTES + lut_gemm_workspace_bytes(M, m, n), 256);
+    return align_up(lut_plan(M, m, n, bits).bytes, 256);
+}
+static size_t lut_lora_addend_bytes(int64_t M, int64_t m, int64_t n) {
+    return lut_lora_dense(M, m, n) ? align_up((size_t)M * m * sizeof(float), 256) : 0;
+}
+static LoraTPlan lora_t_plan(int64_t M, int64_t n, int r) {
+    LoraTPlan p;
+    p.wr = M > LUT_MAX_M;
+    p.rt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+    p.zb = (int)((M + 16 * p.rt - 1) / (16 * p.rt));
+    p.xt = p.wr ? (r / 16 + LORA_T_RWAVES - 1) / LORA_T_RWAVES : r / 16;
+    const int nkb = (int)(n >> 5);
+    int ks;
+    if (p.wr) {  // about one workgroup per CU, at least 16 groups of 32 columns each
+        ks = std::max(1, std::min(std::min(8, nkb / 16), 256 / std::max(1, p.xt * p.zb)));
+    } else {     // two groups of 32 columns per wave, up to 8 splits (measured, M = 1, r = 32, 4096 x 4096 / 4096 x 14336: 10.4 / 20.1 us
+                 // for the whole call against 11.4 / 20.9 with one workgroup per 16 ranks and no exchange)
+        const int waves = p.rt == 4 ? LORA_T_WAVES / 2 : LORA_T_WAVES;
+        ks = std::max(1, std::min(8, (nkb + 2 * waves - 1) / (2 * waves)));
+    }
+    if ((int64_t)p.xt * p.zb > LORA_T_COUNTERS) ks = 1;  // (many row blocks: whole-K workgroups, no tickets)
+    p.kb_per_wg = (nkb + ks - 1) / ks;
+    p.KS = (nkb + p.kb_per_wg - 1) / p.kb_per_wg;
+    p.t_bytes = align_up((size_t)M * r * 2, 256);
+    p.partial_bytes = p.KS == 1 ? 0 : align_up((size_t)p.KS * M * r * sizeof(float), 256);
+    return p;
+}
+
+// t = round(x lora_A^T) [M, r]; tcount: LORA_T_COUNTERS zeroed ints (left zero), tpart: p.partial_bytes of scratch
+static int lora_t(const void* x, const void* lora_A, int dtype, int64_t M, int64_t n, int r, const LoraTPlan& p, void* t, int* tcount,
+                  float* tpart, hipStream_t stream) {
+    ProfScope prof(M > LUT_MAX_M ? KID_LUT_GEMM : KID_LUT_GEMV, stream);
+    const dim3 grid((unsigned)p.xt, (unsigned)p.KS, (unsigned)p.zb);
+    const uint16_t* xp = static_cast<const uint16_t*>(x);
+    const uint16_t* ap = static_cast<const uint16_t*>(lora_A);
+    uint16_t* tp = static_cast<uint16_t*>(t);
+#define GANQ_LORA_T(BF, RTV, NW, WRV)                                                                                                  \
+    hipLaunchKernelGGL((lora_t_kernel<BF, RTV, NW, WRV>), grid, dim3(NW * 64), 0, stream, xp, ap, (int)M, (int)n, r, p.kb_per_wg, p.KS, \
+                       tpart, tcount, tp)
+    if (p.wr) {
+        if (dtype == 1) GANQ_LORA_T(true, 4, LORA_T_RWAVES, true);
+        else GANQ_LORA_T(false, 4, LORA_T_RWAVES, true);
+    } else if (dtype == 1) {
+        if (p.rt == 1) GANQ_LORA_T(true, 1, LORA_T_WAVES, false);
+        else if (p.rt == 2) GANQ_LORA_T(true, 2, LORA_T_WAVES, false);
+        else GANQ_LORA_T(true, 4, LORA_T_WAVES / 2, false);
+    } else {
+        if (p.rt == 1) GANQ_LORA_T(false, 1, LORA_T_WAVES, false);
+        else if (p.rt == 2) GANQ_LORA_T(false, 2, LORA_T_WAVES, false);
+        else GANQ_LORA_T(false, 4, LORA_T_WAVES / 2, false);
+    }
+#undef GANQ_LORA_T
+    GANQ_LAUNCH_CHECK();
+    return 0;
+}
+
+static int check_lora_args(const char* who, const void* x, const void* lora_A, int dtype, int64_t M, int64_t n, int r) {
+    if (dtype != 0 && dtype != 1) return fail(-2, "%s: dtype %d (0 = fp16, 1 = bf16)", who, dtype);
+    if (n < 32 || n % 32 != 0 || n > INT32_MAX / 2) return fail(-2, "%s: in_features=%lld must be a multiple of 32", who, (long long)n);
+    if (r < 16 || r > 256 || r % 16 != 0) return fail(-2, "%s: rank %d must be a multiple of 16 in [16, 256]", who, r);
+    if (!x || !lora_A) return fail(-3, "%s: null pointer", who);
+    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(lora_A)) & 15) != 0) return fail(-2, "%s: x and lora_A must be 16-byte aligned", who);
+    if (M > INT32_MAX / 2) return fail(-1, "%s: M too large", who);
+    return 0;
+}
+
+extern "C" size_t ganq_lut_linear_lora_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r) {
+    if (M <= 0 || m <= 0 || n < 32 || r <= 0) return 0;
+    const LoraTPlan p = lora_t_plan(M, n, r);
+    return lut_lora_base_bytes(M, m, n, bits) + p.t_bytes + p.partial_bytes + lut_lora_addend_bytes(M, m, n);
+}
+
+static int lut_linear_fwd_lora(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
+                               const void* lora_B, int r, const float* addend, const LutCsr& csr, int dtype, int64_t M, int64_t m, int64_t n,
+                               int bits, void* y, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (M < 0 || m < 0 || n < 0) return fail(-1, "ganq_lut_linear_fwd_lora: negative shape");
+    if (M == 0 || m == 0) return 0;
+    int rc = check_lut_args("ganq_lut_linear_fwd_lora", dtype, m, n, bits);
+    if (rc) return rc;
+    rc = check_lora_args("ganq_lut_linear_fwd_lora", x, lora_A, dtype, M, n, r);
+    if (rc) return rc;
+    if (!lora_B || (reinterpret_cast<uintptr_t>(lora_B) & 15) != 0) return fail(-2, "ganq_lut_linear_fwd_lora: lora_B must be 16-byte aligned");
+    const LoraTPlan p = lora_t_plan(M, n, r);
+    const size_t base = lut_lora_base_bytes(M, m, n, bits);
+    const size_t need = base + p.t_bytes + p.partial_bytes + lut_lora_addend_bytes(M, m, n);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0)
+        return fail(-4, "ganq_lut_linear_fwd_lora: workspace %zu B < required %zu B (or not 256-byte aligned)", workspace_bytes, need);
+    if (M <= LUT_MAX_M && lut_plan(M, m, n, bits).ob > LORA_T_COUNTER0)
+        return fail(-2, "ganq_lut_linear_fwd_lora: out_features=%lld needs more ticket counters than the adapter path leaves", (long long)m);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    char* ws = static_cast<char*>(workspace);
+    uint16_t* t = reinterpret_cast<uint16_t*>(ws + base);
+    rc = lora_t(x, lora_A, dtype, M, n, r, p, t, reinterpret_cast<int*>(ws) + LORA_T_COUNTER0, reinterpret_cast<float*>(ws + base + p.t_bytes), stream);
+    if (rc) return rc;
+    if (lut_lora_dense(M, m, n)) {
+        // dense regime: P = t lora_B^T (+ addend) in fp32, then the plain call with P as its addend (dequantise once + gemm_h16)
+        float* P = reinterpret_cast<float*>(ws + base + p.t_bytes + p.partial_bytes);
+        const dim3 grid((unsigned)((m + 63) / 64), (unsigned)((M + 63) / 64));
+        {
+            ProfScope prof(KID_LUT_GEMM, stream);
+            if (dtype == 1)
+                hipLaunchKernelGGL(lora_addend_kernel<true>, grid, dim3(256), 0, stream, t, static_cast<const uint16_t*>(lora_B), addend, (int)M,
+                                   (int)m, r, P);
+            else
+                hipLaunchKernelGGL(lora_addend_kernel<false>, grid, dim3(256), 0, stream, t, static_cast<const uint16_t*>(lora_B), addend, (int)M,
+                                   (int)m, r, P);
+            GANQ_LAUNCH_CHECK();
+        }
+        return lut_linear_fwd(x, qweight, lut, bias, P, dtype, M, m, n, bits, y, workspace, base, stream_);
+    }
+    LutLora lora;
+    lora.t = t;
+    lora.b = static_cast<const uint16_t*>(lora_B);
+    lora.r = r;
+    return lut_linear_fwd(x, qweight, lut, bias, addend, dtype, M, m, n, bits, y, workspace, base, stream_, csr, lora);
+}
+
+extern "C" int ganq_lut_linear_fwd_lora(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
+                                        const void* lora_B, int r, const float* addend, int dtype, int64_t M, int64_t m, int64_t n,
+                                        int bits, void* y, void* workspace, size_t workspace_bytes, void* stream_) {
+    return lut_linear_fwd_lora(x, qweight, lut, bias, lora_A, lora_B, r, addend, LutCsr(), dtype, M, m, n, bits, y, workspace, workspace_bytes,
+                               stream_);
+}
+
+// ... of a layer with sparse outliers as well (CSR by output feature, vals in the activation dtype): at decode sizes the entries
+// are added inside the decode launch, beside the adapter steps; otherwise their fp32 product goes to the tail of the workspace
+// and is the addend (ganq_lut_linear_fwd_outliers' two ways)
+extern "C" size_t ganq_lut_linear_lora_outliers_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r) {
+    if (M <= 0 || m <= 0 || n < 32 || r <= 0) return 0;
+    return align_up(ganq_lut_linear_lora_workspace_bytes(M, m, n, bits, r), 256) + (size_t)M * m * sizeof(float);
+}
+
+extern "C" int ganq_lut_linear_fwd_lora_outliers(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
+                                                 const void* lora_B, int r, const int32_t* rowptr, const int32_t* cols, const void* vals,
+                                                 int dtype, int64_t M, int64_t m, int64_t n, int bits, void* y, void* workspace,
+                                                 size_t workspace_bytes, void* stream_) {
+    if (M < 0 || m < 0 || n < 0) return fail(-1, "ganq_lut_linear_fwd_lora_outliers: negative shape");
+    if (M == 0 || m == 0) return 0;
+    if (n < 32 || n % 32 != 0 || r <= 0) return fail(-2, "ganq_lut_linear_fwd_lora_outliers: in_features=%lld, rank %d", (long long)n, r);
+    if (!rowptr) return fail(-3, "ganq_lut_linear_fwd_lora_outliers: null rowptr");
+    const size_t base = align_up(ganq_lut_linear_lora_workspace_bytes(M, m, n, bits, r), 256);
+    if (!workspace || workspace_bytes < base + (size_t)M * m * sizeof(float))
+        return fail(-4, "ganq_lut_linear_fwd_lora_outliers: workspace %zu B < required %zu B", workspace_bytes,
+                    base + (size_t)M * m * sizeof(float));
+    if (M <= LUT_MAX_M && (bits == 2 || bits == 3 || bits == 4) && lut_plan(M, m, n, bits).inwg) {
+        LutCsr csr;
+        csr.rowptr = rowptr;
+        csr.cols = cols;
+        csr.vals = static_cast<const uint16_t*>(vals);
+        return lut_linear_fwd_lora(x, qweight, lut, bias, lora_A, lora_B, r, nullptr, csr, dtype, M, m, n, bits, y, workspace, base, stream_);
+    }
+    float* addend = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
+    int rc = ganq_outlier_matmul(x, dtype, M, m, n, rowptr, cols, vals, addend, stream_);
+    if (rc) return rc;
+    return lut_linear_fwd_lora(x, qweight, lut, bias, lora_A, lora_B, r, addend, LutCsr(), dtype, M, m, n, bits, y, workspace, base, stream_);
 }
 
 extern "C" int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits,

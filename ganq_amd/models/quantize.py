@@ -7,6 +7,8 @@ save/load       the packed format the reference lacks: it can only save FORMAT.F
                    load even that (config.py:369,398-401).  Here: one safetensors file with, per quantized Linear,
                    `<name>.qweight` int32 [in*bits/32, out], `<name>.lut` fp16 [out, 2^bits], `<name>.bias`; every other
                    tensor of the model unchanged; `quantize_config.json` next to it with the per-module bit widths.
+                   A layer with an adapter adds `<name>.lora_A` fp16 [r, in] / `<name>.lora_B` fp16 [out, r] to the same
+                   file and `"adapter_rank": r` to its entry of `"modules"` (absent in older checkpoints: no adapter).
 gptq_style_ppl  the evaluator behind the README numbers (examples/quantization/basic_usage_wikitext2.py:63-93):
                    non-overlapping windows of `seqlen` tokens, mean token NLL, exp.
 """
@@ -19,6 +21,7 @@ import torch.nn as nn
 
 from ..looper.gptq_processor import GPTQProcessor
 from ..looper.module_looper import ModuleLooper
+from ..adapter import Lora
 from ..nn_modules.qlinear.ganq_hip import GanqHipQuantLinear
 from ..quantization.config import FORMAT, QuantizeConfig
 from .definitions import LayerMap, layer_map_for
@@ -76,6 +79,9 @@ def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: 
     # several ranks, dist_mode="rows" (the default): calibration is data-parallel -- this rank embeds and forwards only the
     # batches rank, rank + world, ...
     local = dist.world > 1 and looper_options.get("dist_mode", "rows") == "rows"
+    if qcfg.adapter is not None and dist.world > 1:
+        raise NotImplementedError("QuantizeConfig.adapter with several ranks: the row shards would have to exchange the "
+                                  "quantization error (and the layer mode the adapters); quantize on one GPU")
     batches = [b.to(dev) for b in (calibration[dist.rank::dist.world] if local else calibration)]
     was_training = model.training
     model.eval()
@@ -102,10 +108,12 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
         raise ValueError("save_quantized: no QuantizeConfig given and the model carries none")
     os.makedirs(path, exist_ok=True)
     modules = {n: {"bits": m.bits, "in_features": m.in_features, "out_features": m.out_features,
-                   "bias": m.bias is not None, "outliers": int(getattr(m, "outliers", 0))}
+                   "bias": m.bias is not None, "outliers": int(getattr(m, "outliers", 0)),
+                   **({"adapter_rank": int(m.adapter_rank)} if getattr(m, "adapter_rank", 0) else {})}
                for n, m in model.named_modules() if isinstance(m, GanqHipQuantLinear)}
     # the codebook is stored as fp16 also while it trains as an fp32 parameter (train_codebook): the format does not change
-    luts = {f"{n}.lut" for n in modules}
+    # (likewise the adapter while it trains, train_adapter)
+    luts = {f"{n}.{k}" for n in modules for k in ("lut", "lora_A", "lora_B")}
     state = {k: (v.detach().to(torch.float16) if k in luts else v.detach()).contiguous().cpu() for k, v in model.state_dict().items()}
     # tied weights (lm_head <-> embeddings) share storage: safetensors wants each tensor once
     seen, out = {}, {}
@@ -136,7 +144,8 @@ def load_quantized(model: nn.Module, path: str) -> nn.Module:
         lin = named[name]
         q = GanqHipQuantLinear(bits=info["bits"], group_size=qcfg.group_size, sym=qcfg.sym, desc_act=qcfg.desc_act,
                                in_features=info["in_features"], out_features=info["out_features"], bias=info["bias"],
-                               pack_dtype=torch.int32, name=name, outliers=info.get("outliers", 0)).to(lin.weight.device)
+                               pack_dtype=torch.int32, name=name, outliers=info.get("outliers", 0),
+                               adapter=Lora(rank=info["adapter_rank"]) if info.get("adapter_rank") else None).to(lin.weight.device)
         parent, _, child = name.rpartition(".")
         setattr(named[parent] if parent else model, child, q)
     state = load_file(os.path.join(path, "model.safetensors"))

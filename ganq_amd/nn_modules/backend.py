@@ -5,8 +5,8 @@ reduced to the one format this path adds (FORMAT.GANQ_LUT -> BACKEND.GANQ_HIP ->
 reference's FORMAT.FAKE (dequantised weights stay in the nn.Linear modules; nothing to pack).
 
 What differs from the reference's pack path, and why: a LUT layer cannot be rebuilt from the dequantised `linear` alone, so
-`quant_result[name]` carries `ganq_q` / `ganq_lut` (/ `ganq_outliers`) beside scale / zero / g_idx and `pack_module` hands
-them to `pack()`; packing runs on the device the module lives on (the reference moves every
+`quant_result[name]` carries `ganq_q` / `ganq_lut` (/ `ganq_outliers`, / `lora_A`, `lora_B`, `adapter_rank` of an EoRA adapter)
+beside scale / zero / g_idx and `pack_module` hands them to `pack()`; packing runs on the device the module lives on (the reference moves every
 module to the CPU first, utils/model.py:557-563 -- its packers are CPU loops, this one is a HIP kernel).
 """
 from collections import OrderedDict
@@ -16,6 +16,7 @@ from typing import Any, Dict, List, Optional, Type, Union
 import torch
 import torch.nn as nn
 
+from ..adapter import Lora
 from ..quantization.config import FORMAT
 from .qlinear import BaseQuantLinear
 from .qlinear.ganq_hip import GanqHipQuantLinear
@@ -98,9 +99,12 @@ def create_quant_layer(linear_cls: Type[BaseQuantLinear], bits: int, desc_act: b
     try:
         for name, res, lin, in_f, out_f in todo:
             nnz = 0 if res.get("ganq_outliers") is None else int(res["ganq_outliers"][1].numel())
+            # a generated adapter: the module's own rank (dynamic overrides) decides.  Otherwise the caller's `adapter` object (it
+            # may carry tensors to start from) goes to the layer as it is
+            mod_adapter = Lora(rank=int(res["adapter_rank"])) if res.get("adapter_rank") else adapter
             new = linear_cls(bits=res.get("bits", bits), group_size=group_size, desc_act=desc_act, sym=sym, in_features=in_f,
                              out_features=out_f, pack_dtype=pack_dtype, bias=lin.bias is not None, name=name,
-                             lm_head_name=lm_head_name, backend=backend, adapter=adapter, outliers=nnz).to(lin.weight.device)
+                             lm_head_name=lm_head_name, backend=backend, adapter=mod_adapter, outliers=nnz).to(lin.weight.device)
             # the quantized nn.Linear, until pack_module has consumed it.  Not through nn.Module.__setattr__: that would register
             # it as a submodule of the new layer (named_modules / state_dict / parameters would carry the fp weights twice)
             object.__setattr__(new, "_packed_from", lin)
@@ -122,7 +126,7 @@ def make_quant(module: nn.Module, quant_result, qcfg, backend: BACKEND, lm_head_
         return None  # FORMAT.FAKE: nothing to build
     candidates = select_quant_linear(bits=qcfg.bits, group_size=qcfg.group_size, desc_act=qcfg.desc_act, sym=qcfg.sym,
                                      backend=backend, format=qcfg.format, pack=pack, dynamic=qcfg.dynamic, device=device,
-                                     pack_dtype=qcfg.pack_dtype, multi_select=True)
+                                     pack_dtype=qcfg.pack_dtype, multi_select=True, adapter=getattr(qcfg, "adapter", None))
     for cls in candidates:
         try:
             return create_quant_layer(linear_cls=cls, bits=qcfg.bits, desc_act=qcfg.desc_act, dynamic=qcfg.dynamic,
@@ -139,7 +143,8 @@ def pack_module(name: str, qmodules: Dict[str, BaseQuantLinear], quant_result: D
     r = quant_result[name]
     q = qmodules[name]
     q.pack(q._packed_from, r["scale"], r["zero"], r["g_idx"], ganq_indices=r["ganq_q"], ganq_codebook=r["ganq_lut"],
-           ganq_outliers=r.get("ganq_outliers"))
+           ganq_outliers=r.get("ganq_outliers"),
+           ganq_lora=(r["lora_A"], r["lora_B"]) if r.get("adapter_rank") else None)
     object.__delattr__(q, "_packed_from")
 
 

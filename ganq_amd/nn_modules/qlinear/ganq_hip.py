@@ -11,11 +11,22 @@ With the outlier split (`QuantizeConfig.ganq_outlier_ratio`, paper section 3.3) 
   outlier_rowptr int32 [out_features + 1], outlier_cols int32 [nnz], outlier_vals fp16 [nnz]   (CSR by output feature)
 and `forward` == `F.linear(x, lut.gather(1, Q) + W_sparse, bias)`.
 
+With a low-rank adapter (`adapter=Lora(rank=r)`: LoRA / the EoRA adapters `quantize_model` generates) the layer owns two more
+fp16 buffers in PEFT orientation, both contiguous along the dimension the kernels reduce over,
+  lora_A   fp16  [r, in_features]      lora_B   fp16  [out_features, r]      (r a multiple of 16, at most 256)
+and `forward` == round(x Wq^T + x W_sparse^T + t lora_B^T + bias) with t = round(x lora_A^T): fp32 accumulation, ONE rounding of
+y; the intermediate t IS rounded once to the activation dtype (it is the matrix-core operand of the second product; the
+reference rounds it too).  One library call (`_lib.lut_linear_lora`): t by a small HIP kernel, then the LUT kernel of the
+regime runs r / 32 further matrix-core steps on (t, lora_B) -- no library GEMM beside the layer.  A layer without an adapter
+makes exactly the calls it made before.
+
 Training (the reference's FakeQuantLinear is an F.linear on a buffer, so autograd reaches its input): with grad mode on and
 `x` or `lut` requiring grad, `forward` goes through `_GanqLutLinearFn`, whose backward runs the HIP kernels of
 csrc/lut_backward.hip -- dx = dy @ (Wq + W_sparse) (one rounding) and, after `train_codebook(True)`,
 dlut[o][v] = sum of dy[b][o] x[b][j] over the j with Q[o][j] == v.  `qweight` (the indices), `bias` and the outlier values
-are frozen buffers: they never receive a gradient.  Otherwise (inference, no_grad) `forward` makes exactly the call it
+are frozen buffers: they never receive a gradient.  With an adapter the training forward is composed in autograd,
+`_GanqLutLinearFn(x) + ((x lora_A^T) lora_B^T)` with the rank-r products as fp32 torch ops (so y is rounded twice there), and
+`train_adapter(True)` turns `lora_A` / `lora_B` into fp32 parameters under the same state_dict keys.  Otherwise (inference, no_grad) `forward` makes exactly the call it
 always made: same launches, no grad_fn.
 
 `pack()` keeps the reference signature `(linear, scales, zeros, g_idx)` (utils/model.py:552-570): because that
@@ -27,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
+from ...adapter import Lora, validate_rank
 from . import BaseQuantLinear
 
 BACKEND_GANQ_HIP = "ganq_hip"
@@ -46,7 +58,7 @@ class GanqHipQuantLinear(BaseQuantLinear):
     SUPPORTS_DEVICES = ["cuda"]  # ROCm presents as "cuda" in torch (models/_const.py:34,46)
     SUPPORTS_PLATFORM = ["linux"]
     SUPPORTS_PACK_DTYPES = [torch.int32]
-    SUPPORTS_ADAPTERS = []
+    SUPPORTS_ADAPTERS = [Lora]
     SUPPORTS_DTYPES = [torch.float16, torch.bfloat16]
 
     QUANT_TYPE = "ganq_hip"
@@ -67,6 +79,21 @@ class GanqHipQuantLinear(BaseQuantLinear):
             self.register_buffer("outlier_rowptr", torch.zeros(out_features + 1, dtype=torch.int32))
             self.register_buffer("outlier_cols", torch.zeros(self.outliers, dtype=torch.int32))
             self.register_buffer("outlier_vals", torch.zeros(self.outliers, dtype=torch.float16))
+        self.adapter_rank = 0  # 0: no adapter, no extra buffers
+        if adapter is not None:
+            self.adapter_rank = validate_rank(adapter.rank, "GanqHipQuantLinear: `adapter`")
+            self.register_buffer("lora_A", torch.zeros((self.adapter_rank, in_features), dtype=torch.float16))
+            self.register_buffer("lora_B", torch.zeros((out_features, self.adapter_rank), dtype=torch.float16))
+            if adapter.lora_A is not None and adapter.lora_B is not None:  # reference attribute orientation: the transposes
+                self._set_lora(adapter.lora_A.t(), adapter.lora_B.t())
+
+    def _set_lora(self, A: torch.Tensor, B: torch.Tensor):
+        r = self.adapter_rank
+        if tuple(A.shape) != (r, self.in_features) or tuple(B.shape) != (self.out_features, r):
+            raise ValueError(f"adapter tensors {tuple(A.shape)} / {tuple(B.shape)} do not fit lora_A [{r}, {self.in_features}] / "
+                             f"lora_B [{self.out_features}, {r}]")
+        self.lora_A = A.detach().to(device=self.lora_A.device, dtype=torch.float16).contiguous()
+        self.lora_B = B.detach().to(device=self.lora_B.device, dtype=torch.float16).contiguous()
 
     def post_init(self):
         pass
@@ -91,7 +118,15 @@ class GanqHipQuantLinear(BaseQuantLinear):
 
     def pack(self, linear: nn.Module, scales: torch.Tensor = None, zeros: torch.Tensor = None,
              g_idx: torch.Tensor = None, ganq_indices: torch.Tensor = None, ganq_codebook: torch.Tensor = None,
-             ganq_outliers=None):
+             ganq_outliers=None, ganq_lora=None):
+        """ganq_lora: (lora_A [r, in_features], lora_B [out_features, r]) of a layer built with `adapter=Lora(rank=r)`"""
+        if self.adapter_rank and ganq_lora is None and getattr(self.adapter, "lora_A", None) is None:
+            raise ValueError("a layer with an adapter cannot be recovered from its weight: pass ganq_lora= (or build the layer "
+                             "from an adapter object that carries lora_A / lora_B)")
+        if ganq_lora is not None:
+            if not self.adapter_rank:
+                raise ValueError("ganq_lora= given to a layer that was built without an adapter")
+            self._set_lora(*ganq_lora)
         W = linear.weight.data
         if type(linear).__name__ == "Conv1D":
             W = W.t()
@@ -132,6 +167,27 @@ class GanqHipQuantLinear(BaseQuantLinear):
         Wq = _lib.lut_dequant(self.qweight, self.lut, self.in_features, self.bits)
         return Wq + self._sparse_dense(Wq.dtype) if self.outliers else Wq
 
+    def merged_weight(self) -> torch.Tensor:
+        """dequantize_weight() + lora_B @ lora_A: the dense weight the layer's forward is equivalent to (tests, export)"""
+        W = self.dequantize_weight()
+        if not self.adapter_rank:
+            return W
+        return (W.float() + self.lora_B.detach().float() @ self.lora_A.detach().float()).to(W.dtype)
+
+    def train_adapter(self, enabled: bool = True):
+        """enabled: `lora_A` / `lora_B` become fp32 nn.Parameters (master copies; the training forward uses them in fp32).
+        False: back to fp16 buffers, rounded once.  Names and so the state_dict keys stay `lora_A` / `lora_B`."""
+        if not self.adapter_rank:
+            raise ValueError("train_adapter: the layer has no adapter")
+        for name in ("lora_A", "lora_B"):
+            t = getattr(self, name).detach()
+            delattr(self, name)
+            if enabled:
+                setattr(self, name, nn.Parameter(t.to(torch.float32).clone()))
+            else:
+                self.register_buffer(name, t.to(torch.float16).contiguous())
+        return self
+
     def train_codebook(self, enabled: bool = True):
         """enabled: `lut` becomes an fp32 nn.Parameter (the master copy; each forward rounds it to the activation dtype and
         its gradient passes straight through that rounding).  False: back to an fp16 buffer, rounded once.  The name and so
@@ -166,7 +222,28 @@ class GanqHipQuantLinear(BaseQuantLinear):
             vals_by_dtype[dtype] = self.outlier_vals[order].to(dtype).contiguous()
         return rowptr_t, cols_t, vals_by_dtype[dtype]
 
-    def _lut_forward(self, x2: torch.Tensor, lut: torch.Tensor, bias):
+    def _lora_as(self, dtype):
+        """(lora_A, lora_B) in the activation dtype for the inference call: the buffers themselves when they have it, else a copy
+        converted once and kept until a factor is replaced or written in place (bf16 activations, train_adapter's fp32 masters)"""
+        A, B = self.lora_A.detach(), self.lora_B.detach()
+        if A.dtype == dtype and B.dtype == dtype:
+            return A, B
+        key = (dtype, A.data_ptr(), A._version, B.data_ptr(), B._version)
+        cache = getattr(self, "_lora_cache", None)
+        if cache is None or cache[0] != key:
+            cache = (key, A.to(dtype).contiguous(), B.to(dtype).contiguous())
+            object.__setattr__(self, "_lora_cache", cache)
+        return cache[1], cache[2]
+
+    def _lut_forward(self, x2: torch.Tensor, lut: torch.Tensor, bias, lora=None):
+        if lora is not None:
+            # adapter: t = x lora_A^T and the r / 32 further steps of the LUT kernel in one library call; the outliers of a layer go
+            # with it (inside the decode launch at decode sizes, as the fp32 addend otherwise)
+            outl = None
+            if self.outliers:
+                vals = self.outlier_vals if self.outlier_vals.dtype == x2.dtype else self.outlier_vals.to(x2.dtype)
+                outl = (self.outlier_rowptr, self.outlier_cols, vals)
+            return _lib.lut_linear_lora(x2, self.qweight, lut, bias, self.bits, lora[0], lora[1], outliers=outl)
         # one C-ABI entry for every batch size: the decode kernels up to 64 rows, the fused LUT-dequant GEMM above
         # (csrc/lut_gemm.hip) -- the dequantised weight is never materialised and no library GEMM is called
         if self.outliers:  # x @ W_sparse^T in fp32, added inside the LUT kernel before its one rounding
@@ -179,13 +256,25 @@ class GanqHipQuantLinear(BaseQuantLinear):
             raise _lib.GanqHipError("GanqHipQuantLinear runs on the GPU only (no CPU fallback)")
         out_shape = x.shape[:-1] + (self.out_features,)
         x2 = x.reshape(-1, self.in_features)
-        if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad):
-            return _GanqLutLinearFn.apply(x2, self.lut, self).reshape(out_shape)
+        if not self.adapter_rank:
+            if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad):
+                return _GanqLutLinearFn.apply(x2, self.lut, self).reshape(out_shape)
+            lut, bias = self.lut, self.bias
+            if lut.dtype != x.dtype:
+                lut = lut.to(x.dtype)
+                bias = None if bias is None else bias.to(x.dtype)
+            return self._lut_forward(x2, lut, bias).reshape(out_shape)
+        if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad or self.lora_A.requires_grad
+                                        or self.lora_B.requires_grad):
+            # training: the adapter term in autograd around the LUT function (rank-r products, fp32)
+            y = _GanqLutLinearFn.apply(x2, self.lut, self)
+            t = x2.float() @ self.lora_A.float().t()
+            return (y + (t @ self.lora_B.float().t()).to(y.dtype)).reshape(out_shape)
         lut, bias = self.lut, self.bias
         if lut.dtype != x.dtype:
             lut = lut.to(x.dtype)
             bias = None if bias is None else bias.to(x.dtype)
-        return self._lut_forward(x2, lut, bias).reshape(out_shape)
+        return self._lut_forward(x2, lut.detach(), bias, self._lora_as(x.dtype)).reshape(out_shape)
 
 
 class _GanqLutLinearFn(torch.autograd.Function):

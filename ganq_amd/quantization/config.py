@@ -1,6 +1,7 @@
 """QuantizeConfig for the GANQ path -- same field names, defaults and validation as the reference
 (gptqmodel/quantization/config.py:157-289) for every field the path reads; fields of unrelated
-methods (adapters, rotation, marlin, ...) are not carried.
+methods (rotation, marlin, ...) are not carried.  `adapter` is: a `Lora` (or its dict) asks for an EoRA adapter of that rank
+on every packed module (looper/gptq_processor.py), `dynamic` may override the rank per module or switch it off.
 
 One addition: FORMAT.GANQ_LUT.  The reference saves GANQ output as FORMAT.FAKE (dequantised fp16 weights,
 config.py:75,103-105); the LUT layer needs the indices and codebooks, so QUANT_METHOD.GANQ maps to
@@ -12,6 +13,8 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Dict, Optional, Union
 
 import torch
+
+from ..adapter import Lora, normalize_adapter, validate_rank
 
 
 class FORMAT:
@@ -78,9 +81,17 @@ class QuantizeConfig:
     # passes run (134 MB at in_features 4096, 470 MB at 14336; at most quantization.gptq.STAGE_MAX_LIVE per device, freed
     # when the passes end).
     ganq_hessian_stage_tokens: int = field(default=16384)
+    # reference field (config.py `adapter`): a Lora (or {"name": "lora", "rank": r}) -> every packed module gets a training-free
+    # EoRA adapter of rank r, generated right after its quantization.  Rank: a positive multiple of 16, at most 256.
+    adapter: Optional[Union[Dict[str, Any], Lora]] = field(default=None)
 
     def __post_init__(self):
         info = fields(self)
+        self.adapter = normalize_adapter(self.adapter)
+        if self.adapter is not None:
+            validate_rank(self.adapter.rank, "QuantizeConfig: `adapter`")
+            if self.format == FORMAT.FAKE:
+                raise ValueError("QuantizeConfig: `adapter` needs format=`ganq_lut`: a dequantised nn.Linear cannot carry one")
         if self.pack_dtype is None:
             self.pack_dtype = torch.int32
         elif isinstance(self.pack_dtype, str):
@@ -110,6 +121,11 @@ class QuantizeConfig:
                                          f"`{info[0].metadata['choices']}` bits.")
                     if key == "group_size" and value != -1 and value <= 0:
                         raise ValueError("QuantizeConfig: `group_size` must in the value set of `[-1, 16, 32, 64, 128]`.")
+                    if key == "adapter":  # {} or rank 0: no adapter for these modules
+                        if not isinstance(value, dict):
+                            raise ValueError(f"QuantizeConfig: Layer `{layer}`: `adapter` override must be a dict")
+                        if value.get("rank", 0) not in (0, None):
+                            validate_rank(value["rank"], f"QuantizeConfig: Layer `{layer}` `adapter`")
         if self.group_size != -1 and self.group_size <= 0:
             raise ValueError("QuantizeConfig: `group_size` must in the value set of `[-1, 16, 32, 64, 128]`.")
         if not (0 < self.damp_percent < 1):
@@ -132,12 +148,25 @@ class QuantizeConfig:
     def dynamic_get(self, layer_name: str, key: str = None, default: Any = None, sub_key: str = None):
         return dynamic_get(self.dynamic, layer_name, key, default, sub_key)
 
+    def adapter_rank(self, layer_name: str) -> int:
+        """effective adapter rank of a module (eora_processor.py:83-107): the config's rank unless `dynamic` overrides it;
+        `"adapter": {}` or rank 0 switches the adapter off for the module.  0: no adapter."""
+        if self.adapter is None:
+            return 0
+        override = self.dynamic_get(layer_name, "adapter", None)
+        if override is False:  # '-:' pattern: the module is not quantized at all
+            return 0
+        if isinstance(override, dict):
+            return int(override.get("rank", 0) or 0)
+        return int(self.adapter.rank)
+
     def clone(self) -> "QuantizeConfig":
         return copy.deepcopy(self)
 
     def to_dict(self) -> Dict[str, Any]:
         out = {f.name: getattr(self, f.name) for f in fields(self) if f.name not in ("device",)}
         out["pack_dtype"] = str(self.pack_dtype).split(".")[-1]
+        out["adapter"] = None if self.adapter is None else self.adapter.to_dict()
         return out
 
     @classmethod

@@ -9,6 +9,10 @@ assignment and the per-row codebook that `GanqHipQuantLinear` packs.
 `qcfg.ganq_outlier_ratio > 0` adds the outlier split of the paper (section 3.3, Appendix A Algorithm 2; not in the
 reference code): the row-wise tails of W are taken out on the device (`_lib.outlier_split`), GANQ runs on the rest, the
 returned weight is `T.gather(1, Q) + W_sparse`, and `self.ganq_outliers` = (rowptr, cols, vals) is what the layer keeps.
+
+`self.eora_rank > 0` (set by the processor from `QuantizeConfig.adapter`) adds the EoRA adapter (quantization/eora.py) while the
+weight, the quantized weight and the damped Hessian of the loop are still on the device: after `quantize()`,
+`self.eora_A` [r, n] / `self.eora_B` [m, r] (fp16, original column order like the indices), `self.eora_e0`, `self.eora_e`.
 """
 import time
 
@@ -39,6 +43,9 @@ class GANQ(GPTQ):
         # cleared by the looper for the modules of a group it quantizes side by side on one GPU (streams): a helper workgroup
         # of the S-solve may then not be resident with its tile (GANQ_FLAG_NO_HELPERS; same bits either way)
         self.solve_helpers = True
+        self.eora_rank = 0  # > 0: generate an EoRA adapter of this rank after the loop
+        self.eora_A = self.eora_B = None
+        self.eora_e0 = self.eora_e = self.eora_time = None
 
     def _needs_only_hinv_diag(self) -> bool:
         return True
@@ -91,6 +98,16 @@ class GANQ(GPTQ):
             T, Q, dists, best_k = _lib.run_layer(W, self.Xxt_damped, self.L, T0, self.iterations, alias_q=alias,
                                                  helpers=self.solve_helpers)
         Wq, Losses = _lib.dequant_losses(W, T, Q, _hinv_diag(Hinv).contiguous())
+        if self.eora_rank > 0:
+            # Delta = W - (Wq + W_sparse) = W_dense - Wq_dense, with the weight as the loop saw it (dead columns filled, permuted
+            # order) against the matrix the loop minimised against: H after the dead-column fix + damp I, same order
+            from .eora import eora_generate
+
+            torch.cuda.current_stream(W.device).synchronize()  # (so that eora_time does not count the loop's kernels)
+            te = time.perf_counter()
+            self.eora_A, self.eora_B, self.eora_e0, self.eora_e = eora_generate(W - Wq, self.Xxt_damped, self.eora_rank)
+            torch.cuda.current_stream(W.device).synchronize()
+            self.eora_time = time.perf_counter() - te
         if sparse is not None:  # effective weight = dequantised dense part + the exact outliers
             rowptr, cols, vals = sparse
             rows = torch.repeat_interleave(torch.arange(W.shape[0], device=W.device), (rowptr[1:] - rowptr[:-1]).long())
@@ -109,6 +126,8 @@ class GANQ(GPTQ):
     def _unpermute_state(self, invperm):
         # gptq.py:341-343 un-permutes Wq only when desc_act is set; the indices follow the same rule so that
         # T.gather(1, Q) always equals the returned weight
+        if invperm is not None and self.eora_A is not None:
+            self.eora_A = self.eora_A[:, invperm].contiguous()
         if invperm is not None and self.ganq_indices is not None:
             self.ganq_indices = self.ganq_indices[:, invperm].contiguous()
             if self.ganq_outliers is not None:  # permuted column c is original column perm[c]; keep rows ascending

@@ -213,6 +213,25 @@ size_t ganq_lut_linear_outliers_workspace_bytes(int64_t M, int64_t m, int64_t n,
 int ganq_lut_linear_fwd_outliers(const void* x, const int32_t* qweight, const void* lut, const void* bias,
                                  const int32_t* rowptr, const int32_t* cols, const void* vals, int dtype, int64_t M, int64_t m,
                                  int64_t n, int bits, void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* LUT forward of a layer with a low-rank adapter (LoRA / EoRA): lora_A [r, n], lora_B [m, r] in the activation dtype, both
+ * contiguous along the dimension the kernels reduce over, 16-byte aligned; r a multiple of 16 in [16, 256].
+ *   y = round(x Wq^T + t lora_B^T (+ addend) (+ bias)),   t = round(x lora_A^T) [M, r] in the activation dtype:
+ * fp32 accumulation, ONE rounding of y; t is rounded once (it is the matrix-core operand of the second product).  t is formed in
+ * the workspace by a thin-product kernel of its own; the LUT kernel of the regime
+ * then runs r / 32 further matrix-core steps on (t, lora_B) -- no library GEMM, bitwise repeatable.  With an adapter every
+ * M > 64 goes through the fused LUT-dequant GEMM.  addend: fp32 [M, m] or NULL.  The workspace
+ * is 256-byte aligned and initialised like the plain one (ganq_lut_linear_workspace_init over all of it). */
+size_t ganq_lut_linear_lora_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r);
+int ganq_lut_linear_fwd_lora(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
+                             const void* lora_B, int r, const float* addend, int dtype, int64_t M, int64_t m, int64_t n,
+                             int bits, void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* the same for a layer with sparse outliers (arguments as ganq_lut_linear_fwd_outliers): at decode sizes ONE LUT launch adds the
+ * CSR entries and the adapter steps; otherwise ganq_outlier_matmul into the tail of the workspace is the addend */
+size_t ganq_lut_linear_lora_outliers_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r);
+int ganq_lut_linear_fwd_lora_outliers(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
+                                      const void* lora_B, int r, const int32_t* rowptr, const int32_t* cols, const void* vals,
+                                      int dtype, int64_t M, int64_t m, int64_t n, int bits, void* y, void* workspace,
+                                      size_t workspace_bytes, void* stream);
 /* prefill path: materialise Wq [m,n] = lut[o][index] in the activation dtype for a library GEMM */
 int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits, void* Wq_out,
                      void* stream);

@@ -94,6 +94,7 @@ SIGNATURES = {
     "ganq_lut_linear_bwd_lut_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_linear_bwd_lut": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp,
                                                _c_sz, _c_vp]),
+    "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_outlier_cutoffs": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_extract": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -632,13 +633,35 @@ def lut_dequant(qweight, lut, n: int, bits: int):
     return Wq
 
 
+LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*
+
+
+def debug_lut_plan(M: int, m: int, n: int, bits: int, r: int = 0, outliers: bool = False, ncu: int = 0, device=None) -> dict:
+    """which kernels the LUT forward launches for x [M,n] on a layer [m,n] under the current developer options
+    (ganq_debug_lut_plan).  ncu > 0: plan for that many compute units, no GPU needed; 0: those of `device` (default: the current
+    one).  outliers / adapter: None without them, "fused" inside the LUT launch, "addend" as an fp32 product added by it."""
+    out = (ctypes.c_int * 8)()
+    args = (int(M), int(m), int(n), int(bits), int(r), 1 if outliers else 0, int(ncu), ctypes.cast(out, _c_vp), 8)
+    if ncu > 0:
+        _check(lib().ganq_debug_lut_plan(*args), "ganq_debug_lut_plan")
+    else:
+        with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+            _check(lib().ganq_debug_lut_plan(*args), "ganq_debug_lut_plan")
+    mode = {-1: None, 1: "fused", 0: "addend"}
+    return dict(regime=LUT_REGIMES[out[0]], row_tiles=out[1], KS=out[2], outliers=mode[out[3]], adapter=mode[out[4]], t_KS=out[5],
+                workgroups=out[6], ncu=out[7])
+
+
 _LUT_WS = {}  # (device index, stream) -> zero-initialised workspace, kept across calls (the kernel leaves it clean)
+_LUT_WS_RETIRED = []  # workspaces a larger one superseded: a captured HIP graph may still point into them, so they live as long as the process
 
 
 def _lut_workspace(nbytes: int, device):
     key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(device))
     ws = _LUT_WS.get(key)
     if ws is None or ws.numel() < nbytes:
+        if ws is not None:
+            _LUT_WS_RETIRED.append(ws)
         ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _call("ganq_lut_linear_workspace_init", (ws,), ws.data_ptr(), ws.numel(), _ST)
         _LUT_WS[key] = ws

@@ -92,6 +92,7 @@ int ensure_dynamic_lds(const void* func, size_t bytes);
 
 // dense fp16 / bf16 GEMM of the LUT forward's prefill path (gemm_h16.hip): y[M,N] = x[M,K] @ w[N,K]^T (+ bias) (+ addend)
 bool gemm_h16_supported(int64_t M, int64_t N, int64_t K);
+bool gemm_h16_big(int64_t M, int64_t N, int ncu = 0);  // 256-row tiles (else 128-row tiles); ncu: see plan_cus
 int gemm_h16(const void* x, const void* w, const void* bias, const float* addend, int dtype, int64_t M, int64_t N, int64_t K, void* y,
              hipStream_t stream);
 
@@ -117,6 +118,8 @@ int hessian_w4(float* H, const void* Xt, int64_t ldt, int dtype, int64_t rows, i
 
 // compute units of the CURRENT device (cached per device index; 0 on failure)
 int current_device_cus();
+// the CU count a launch plan is made for: `ncu` > 0 as given (ganq_debug_lut_plan without a GPU), else the current device's
+inline int plan_cus(int ncu) { return ncu > 0 ? ncu : (current_device_cus() > 0 ? current_device_cus() : 1); }
 
 // ---- optional per-kernel timing (profile.hip) ----
 enum KernelId : int {

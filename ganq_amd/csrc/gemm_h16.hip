@@ -559,14 +559,18 @@ bool gemm_h16_supported(int64_t M, int64_t N, int64_t K) {
 }
 
 // BM: 256-row tiles when they fill at least 7/8 of the chip once, else 128-row tiles (twice the workgroups)
+bool gemm_h16_big(int64_t M, int64_t N, int ncu) {
+    const int64_t t256 = ((M + 255) / 256) * ((N + HBN - 1) / HBN);
+    const long long force = opt_get(OPT_GEMM_H16_BM);
+    return force > 0 ? force >= 256 : 8 * t256 >= 7 * (int64_t)plan_cus(ncu);  // (224 tiles of 256 rows on 256 CUs: 112 us against 139 us with 128-row tiles)
+}
+
 int gemm_h16(const void* x, const void* w, const void* bias, const float* addend, int dtype, int64_t M, int64_t N, int64_t K, void* y,
              hipStream_t stream) {
     if (!gemm_h16_supported(M, N, K)) return fail(-1, "gemm_h16: shape %lld x %lld x %lld not supported", (long long)M, (long long)N, (long long)K);
-    const int ncu = std::max(1, current_device_cus());
     const int tiles_n = (int)((N + HBN - 1) / HBN);
-    const int64_t t256 = ((M + 255) / 256) * tiles_n;
     const long long force = opt_get(OPT_GEMM_H16_BM);
-    const bool big = force > 0 ? force >= 256 : 8 * t256 >= 7 * ncu;  // (224 tiles of 256 rows on 256 CUs: 112 us against 139 us with 128-row tiles)
+    const bool big = gemm_h16_big(M, N);
     if (force == 512) {  // developer: the four-wave kernel (128 x 128 wave tiles)
         const int tiles_m = (int)((M + 255) / 256);
         const size_t lds = 4 * (size_t)(256 + HBN) * 32 * 2;  // four stages of 32-wide slices
@@ -615,11 +619,8 @@ int gemm_h16(const void* x, const void* w, const void* bias, const float* addend
 int gemm_h16_buckets(const void* xt, const void* wt, const uint32_t* qw, int bits, int dtype, int64_t M, int64_t N, int64_t K, float* bpart,
                      hipStream_t stream) {
     if (!gemm_h16_supported(M, N, K)) return fail(-1, "gemm_h16_buckets: shape %lld x %lld x %lld not supported", (long long)M, (long long)N, (long long)K);
-    const int ncu = std::max(1, current_device_cus());
     const int tiles_n = (int)((N + HBN - 1) / HBN);
-    const int64_t t256 = ((M + 255) / 256) * tiles_n;
-    const long long force = opt_get(OPT_GEMM_H16_BM);
-    const bool big = force > 0 ? force >= 256 : 8 * t256 >= 7 * ncu;
+    const bool big = gemm_h16_big(M, N);
     const uint16_t* xp = static_cast<const uint16_t*>(xt);
     const uint16_t* wp = static_cast<const uint16_t*>(wt);
 #define GANQ_H16B_LAUNCH(BF, BMV, BB)                                                                                                 \

@@ -557,7 +557,7 @@ struct GemmPlan {
     int tiles_m, tiles_n, KS, st_per;
     size_t partial_bytes;
 };
-GemmPlan lut_gemm_plan(int64_t M, int64_t m, int64_t n) {
+GemmPlan lut_gemm_plan(int64_t M, int64_t m, int64_t n, int ncu_ = 0) {
     GemmPlan p;
     p.tiles_m = (int)((M + GBM - 1) / GBM);
     p.tiles_n = (int)((m + GBN - 1) / GBN);
@@ -566,13 +566,34 @@ GemmPlan lut_gemm_plan(int64_t M, int64_t m, int64_t n) {
     // split in_features while the launch has fewer workgroups than CUs, every split keeping at least 8 stages (512 columns)
     const int force = (int)opt_get(OPT_LUT_GEMM_RM);  // developer switch: forced split factor
     int ks = 1;
-    const int ncu = std::max(1, current_device_cus());
+    const int ncu = plan_cus(ncu_);
     while (ks < 8 && tiles * ks < ncu && nst / (2 * ks) >= 8) ks *= 2;
     if (force > 0) ks = std::min(force, nst);
     p.st_per = (nst + ks - 1) / ks;
     p.KS = (nst + p.st_per - 1) / p.st_per;
     p.partial_bytes = p.KS > 1 ? align_up((size_t)p.KS * (size_t)M * (size_t)m * sizeof(float), 256) : 0;
     return p;
+}
+
+// whole-K launches: the one-workgroup-per-CU pipelined kernel or the two-workgroups-per-CU one.
+// measured (4-bit, fp16, both kernels with buffer loads): about one tile per CU (4096 x 4096, M = 2048: 256 tiles) 87 us
+// pipelined vs 103 us with the two-workgroups-per-CU kernel; 512 tiles (M = 4096) 175 vs 164; 896 tiles (14336 x 4096,
+// M = 2048) 310 vs 287; 1792 tiles (M = 4096) 556 vs 520: the pipelined kernel where a CU gets one tile, the other above
+// (a layer with an adapter takes the two-workgroups-per-CU kernel: the pipelined one has no adapter stages)
+static bool lut_gemm_pipe(const GemmPlan& p, bool lora, int ncu_ = 0) {
+    const int pipe_opt = (int)opt_get(OPT_LUT_GEMM_PIPE);
+    const int64_t ntile = (int64_t)p.tiles_m * p.tiles_n;
+    const int64_t ncu = plan_cus(ncu_);
+    const bool pipe_by_shape = 8 * ntile >= 7 * ncu && 4 * ntile < 7 * ncu;  // 224 <= tiles < 448 on the 256 CUs of an MI355X
+    return !lora && p.KS == 1 && (pipe_opt >= 0 ? pipe_opt != 0 : pipe_by_shape);
+}
+
+// ganq_debug_lut_plan (lut_linear.hip): what lut_gemm() launches for this shape -- kernel 0 whole-K, 1 split-K + reduce, 2 pipelined
+void lut_gemm_describe(int64_t M, int64_t m, int64_t n, bool lora, int ncu, int* kernel, int* tiles_m, int* KS) {
+    const GemmPlan p = lut_gemm_plan(M, m, n, ncu);
+    *kernel = lut_gemm_pipe(p, lora, ncu) ? 2 : (p.KS > 1 ? 1 : 0);
+    *tiles_m = p.tiles_m;
+    *KS = p.KS;
 }
 
 template <int BITS>
@@ -596,20 +617,12 @@ static int launch_gemm_bits(const void* x, const uint32_t* qw, const void* lut, 
             else GANQ_GEMM_LAUNCH1(BF, SP, false, false);              \
         }                                                              \
     } while (0)
-    const int pipe_opt = (int)opt_get(OPT_LUT_GEMM_PIPE);
-    // measured (4-bit, fp16, both kernels with buffer loads): about one tile per CU (4096 x 4096, M = 2048: 256 tiles) 87 us
-    // pipelined vs 103 us with the two-workgroups-per-CU kernel; 512 tiles (M = 4096) 175 vs 164; 896 tiles (14336 x 4096,
-    // M = 2048) 310 vs 287; 1792 tiles (M = 4096) 556 vs 520: the pipelined kernel where a CU gets one tile, the other above
-    const int64_t ntile = (int64_t)p.tiles_m * p.tiles_n;
-    const int64_t ncu = std::max(1, current_device_cus());
-    const bool pipe_by_shape = 8 * ntile >= 7 * ncu && 4 * ntile < 7 * ncu;  // 224 <= tiles < 448 on the 256 CUs of an MI355X
     // the pipelined kernel addresses both operands through 32-bit buffer offsets (incl. one stage of look-ahead)
     const bool fits32 = ((int64_t)M + GBM) * n * 2 < (1ll << 31) && (int64_t)(n >> 5) * BITS * m * 4 < (1ll << 31);
     if (!fits32)
         return fail(-1, "ganq_lut_linear_fwd: x (%lld x %lld) or qweight beyond the 2 GB window of the GEMM's buffer loads: split the "
                         "rows of x over several calls", (long long)M, (long long)n);
-    // (a layer with an adapter takes the two-workgroups-per-CU kernel: the pipelined one has no adapter stages)
-    const bool pipe = !lora.b && p.KS == 1 && (pipe_opt >= 0 ? pipe_opt != 0 : pipe_by_shape);
+    const bool pipe = lut_gemm_pipe(p, lora.b != nullptr);
     if (pipe) {
         const bool ragged = (n & 63) != 0;
 #define GANQ_PIPE_LAUNCH(BF, RG)                                                                                                   \

@@ -965,16 +965,17 @@ int lut_gemm(const void* x, const uint32_t* qw, const void* lut, const void* bia
              int64_t m, int64_t n, int bits, void* y, float* partial, size_t partial_bytes, hipStream_t stream,
              const LutLora& lora = LutLora());
 size_t lut_gemm_workspace_bytes(int64_t M, int64_t m, int64_t n);
+void lut_gemm_describe(int64_t M, int64_t m, int64_t n, bool lora, int ncu, int* kernel, int* tiles_m, int* KS);
 
 // Prefill with many rows: dequantise the layer ONCE into the workspace and run the dense GEMM (gemm_h16.hip) -- every 256-row
 // tile of the fused kernel re-decodes the same weights.  Measured (MI355X, 4-bit fp16, round 4): 4096 x 4096 M = 4096 fused
 // 166 us, dense 116 + dequant; M = 2048 a tie; below, the dense tiles no longer fill the chip and the fused kernel's split of
 // in_features wins.  From >= 1024 rows on, when 256-row tiles give (nearly) every CU one.
-static bool lut_dense_path(int64_t M, int64_t m, int64_t n) {
+static bool lut_dense_path(int64_t M, int64_t m, int64_t n, int ncu_ = 0) {
     const long long thr = opt_get(OPT_LUT_DENSE_M);
     if (thr == 0 || !gemm_h16_supported(M, m, n) || (n & 31) != 0) return false;
     if (thr > 0) return M >= thr;
-    const int ncu = std::max(1, current_device_cus());
+    const int ncu = plan_cus(ncu_);
     const int64_t t128 = ((M + 127) / 128) * ((m + 255) / 256);
     // the dense kernel's smaller tile (128 x 256) fills the chip at least once.  (4096 x 4096 at M = 2048, 256 such tiles: 73 + 12 us
     // against 94 for the fused kernel since the dense kernel walks its tiles in L2-sized blocks; at M = 1024, 128 tiles: 63 + 12
@@ -1220,7 +1221,9 @@ struct LoraTPlan {
 // n.  Measured (4-bit fp16, us, fused kernel with adapter stages / this way): 4096 x 14336 M = 2048 r = 32 393 / 308, M = 4096
 // r = 128 669 / 597; 14336 x 4096 M = 2048 r = 128 331 / 396, M = 4096 r = 32 560 / 617; 4096 x 4096 within 10 % either way.
 constexpr int64_t LORA_DENSE_MIN_N = 8192;
-static bool lut_lora_dense(int64_t M, int64_t m, int64_t n) { return M > LUT_MAX_M && n >= LORA_DENSE_MIN_N && lut_dense_path(M, m, n); }
+static bool lut_lora_dense(int64_t M, int64_t m, int64_t n, int ncu = 0) {
+    return M > LUT_MAX_M && n >= LORA_DENSE_MIN_N && lut_dense_path(M, m, n, ncu);
+}
 static size_t lut_lora_base_bytes(int64_t M, int64_t m, int64_t n, int bits) {
     if (lut_lora_dense(M, m, n)) return align_up(ganq_lut_linear_workspace_bytes(M, m, n, bits), 256);
     if (M > LUT_MAX_M) return align_up(LUT_COUNTER_BYTES + lut_gemm_workspace_bytes(M, m, n), 256);
@@ -1379,6 +1382,53 @@ extern "C" int ganq_lut_linear_fwd_lora_outliers(const void* x, const int32_t* q
     int rc = ganq_outlier_matmul(x, dtype, M, m, n, rowptr, cols, vals, addend, stream_);
     if (rc) return rc;
     return lut_linear_fwd_lora(x, qweight, lut, bias, lora_A, lora_B, r, addend, LutCsr(), dtype, M, m, n, bits, y, workspace, base, stream_);
+}
+
+// tests / developers: which kernels the forward entry points above launch for a shape under the current options, from the plan
+// functions they call themselves.  No GPU is touched when ncu > 0.
+extern "C" int ganq_debug_lut_plan(int64_t M, int64_t m, int64_t n, int bits, int r, int outliers, int ncu, int* out, int out_len) {
+    if (!out || out_len < 8) return fail(-3, "ganq_debug_lut_plan: out must hold 8 ints");
+    if (M <= 0 || m <= 0 || n < 32 || ncu < 0) return fail(-1, "ganq_debug_lut_plan: bad shape");
+    int rc = check_lut_args("ganq_debug_lut_plan", 0, m, n, bits);
+    if (rc) return rc;
+    if (r != 0 && (r < 16 || r > 256 || r % 16 != 0)) return fail(-2, "ganq_debug_lut_plan: rank %d must be 0 or a multiple of 16 in [16, 256]", r);
+    int regime, rt, ks, wgs, outl = -1, adapter = -1, t_ks = 0;
+    if (M > LUT_MAX_M) {
+        if (outliers) outl = 0;  // ganq_outlier_matmul into the tail of the workspace is the addend
+        const bool dense = r ? lut_lora_dense(M, m, n, ncu) : lut_dense_path(M, m, n, ncu);
+        if (dense) {
+            const bool big = gemm_h16_big(M, m, ncu);
+            regime = big ? GANQ_LUT_REGIME_DENSE256 : GANQ_LUT_REGIME_DENSE128;
+            rt = (int)((M + (big ? 255 : 127)) / (big ? 256 : 128));
+            ks = 1;
+            wgs = rt * (int)((m + 255) / 256);
+            if (r) adapter = 0;  // P = t lora_B^T from lora_addend_kernel is the addend
+        } else {
+            int kernel;
+            lut_gemm_describe(M, m, n, r != 0, ncu, &kernel, &rt, &ks);
+            regime = kernel == 2 ? GANQ_LUT_REGIME_GEMM_PIPE : (kernel == 1 ? GANQ_LUT_REGIME_GEMM_SPLITK : GANQ_LUT_REGIME_GEMM);
+            wgs = rt * (int)((m + 127) / 128) * ks;
+            if (r) adapter = 1;
+        }
+    } else {
+        const LutPlan p = lut_plan(M, m, n, bits);
+        regime = p.inwg ? (p.nt == 2 ? GANQ_LUT_REGIME_DECODE32 : GANQ_LUT_REGIME_DECODE16) : GANQ_LUT_REGIME_MFMA_SMALL;
+        rt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
+        ks = p.KS;
+        wgs = p.ob * p.KS;
+        if (outliers) outl = p.inwg ? 1 : 0;
+        if (r) adapter = 1;
+    }
+    if (r) t_ks = lora_t_plan(M, n, r).KS;
+    out[0] = regime;
+    out[1] = rt;
+    out[2] = ks;
+    out[3] = outl;
+    out[4] = adapter;
+    out[5] = t_ks;
+    out[6] = wgs;
+    out[7] = plan_cus(ncu);
+    return 0;
 }
 
 extern "C" int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits,

@@ -196,7 +196,10 @@ int ganq_prologue_weights(const float* W, const int64_t* perm, const uint8_t* de
  * partial tiles live in the workspace and a second launch sums them in split order (deterministic).
  * The workspace must be zero-filled ONCE after allocation (ganq_lut_linear_workspace_init); every call leaves the
  * counters zero again, so it can be reused by later calls of any shape that fits.  One workspace serves one stream
- * at a time.                                                                                                    */
+ * at a time.
+ * Contract of every sizer below (ganq_lut_linear*_workspace_bytes), enforced by the guarded-buffer tests
+ * (tests/lut_arena.py): a forward call given exactly the returned bytes writes nothing beyond them, nothing outside y's
+ * M * m elements, and leaves the first 64 KB of the workspace (the ticket counters) zero.                        */
 size_t ganq_lut_linear_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
 int ganq_lut_linear_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 int ganq_lut_linear_fwd(const void* x, const int32_t* qweight, const void* lut, const void* bias, int dtype,
@@ -208,7 +211,8 @@ int ganq_lut_linear_fwd_add(const void* x, const int32_t* qweight, const void* l
                             int dtype, int64_t M, int64_t m, int64_t n, int bits, void* y, void* workspace,
                             size_t workspace_bytes, void* stream);
 /* both in one call for a layer with outliers (ganq_outlier_matmul into the tail of the workspace, then the LUT kernel);
- * the workspace is initialised like the plain one (ganq_lut_linear_workspace_init over all of it) */
+ * the workspace is initialised like the plain one (ganq_lut_linear_workspace_init over all of it).  The sizer's contract is
+ * the plain one's: nothing is written beyond the returned bytes, the first 64 KB are left zero. */
 size_t ganq_lut_linear_outliers_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
 int ganq_lut_linear_fwd_outliers(const void* x, const int32_t* qweight, const void* lut, const void* bias,
                                  const int32_t* rowptr, const int32_t* cols, const void* vals, int dtype, int64_t M, int64_t m,
@@ -220,18 +224,42 @@ int ganq_lut_linear_fwd_outliers(const void* x, const int32_t* qweight, const vo
  * the workspace by a thin-product kernel of its own; the LUT kernel of the regime
  * then runs r / 32 further matrix-core steps on (t, lora_B) -- no library GEMM, bitwise repeatable.  With an adapter every
  * M > 64 goes through the fused LUT-dequant GEMM.  addend: fp32 [M, m] or NULL.  The workspace
- * is 256-byte aligned and initialised like the plain one (ganq_lut_linear_workspace_init over all of it). */
+ * is 256-byte aligned and initialised like the plain one (ganq_lut_linear_workspace_init over all of it); the sizer's contract
+ * is the plain one's (nothing written beyond the returned bytes, the first 64 KB -- the adapter's tickets are its last 1024 ints --
+ * left zero). */
 size_t ganq_lut_linear_lora_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r);
 int ganq_lut_linear_fwd_lora(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
                              const void* lora_B, int r, const float* addend, int dtype, int64_t M, int64_t m, int64_t n,
                              int bits, void* y, void* workspace, size_t workspace_bytes, void* stream);
 /* the same for a layer with sparse outliers (arguments as ganq_lut_linear_fwd_outliers): at decode sizes ONE LUT launch adds the
- * CSR entries and the adapter steps; otherwise ganq_outlier_matmul into the tail of the workspace is the addend */
+ * CSR entries and the adapter steps; otherwise ganq_outlier_matmul into the tail of the workspace is the addend.  Same sizer
+ * contract: nothing written beyond the returned bytes, the first 64 KB left zero. */
 size_t ganq_lut_linear_lora_outliers_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits, int r);
 int ganq_lut_linear_fwd_lora_outliers(const void* x, const int32_t* qweight, const void* lut, const void* bias, const void* lora_A,
                                       const void* lora_B, int r, const int32_t* rowptr, const int32_t* cols, const void* vals,
                                       int dtype, int64_t M, int64_t m, int64_t n, int bits, void* y, void* workspace,
                                       size_t workspace_bytes, void* stream);
+/* tests / developers (host only; no GPU is touched when ncu > 0): which kernels the forward entry points above launch for x [M,n]
+ * and a layer [m,n] of `bits` with an adapter of rank r (0: none) and with / without sparse outliers, under the current developer
+ * options, computed by the plan functions the forward itself calls.  ncu: compute units to plan for, 0 = the current device's.
+ * out[8] = { regime (GANQ_LUT_REGIME_*),
+ *            row tiles: 16-row tiles per workgroup (1, 2, 4) for M <= 64, tiles of 256 / 128 rows of the launch above,
+ *            KS: splits of in_features across workgroups (1: none),
+ *            outliers: -1 none, 1 added inside the decode launch, 0 their fp32 product is the addend,
+ *            adapter: -1 none, 1 further matrix-core steps of the LUT kernel, 0 its fp32 product is the addend of the dense path,
+ *            KS of the adapter's t kernel (0 without an adapter),
+ *            workgroups of the main launch,
+ *            the CU count planned for }.
+ * The four-wave developer kernel of GANQ_GEMM_H16_BM=512 reports as DENSE256. */
+#define GANQ_LUT_REGIME_DECODE16 0    /* M <= 32: 16 waves split in_features inside the workgroup, 16 features per workgroup */
+#define GANQ_LUT_REGIME_DECODE32 1    /* ... 32 features per workgroup (M <= 16, even m) */
+#define GANQ_LUT_REGIME_MFMA_SMALL 2  /* M <= 64: matrix-core kernel, split-K through memory */
+#define GANQ_LUT_REGIME_GEMM 3        /* M > 64: fused LUT-dequant GEMM, whole K */
+#define GANQ_LUT_REGIME_GEMM_SPLITK 4 /* ... in_features split over workgroups + reduce launch */
+#define GANQ_LUT_REGIME_GEMM_PIPE 5   /* ... one-workgroup-per-CU pipelined kernel */
+#define GANQ_LUT_REGIME_DENSE128 6    /* dequantise once + dense GEMM, 128-row tiles */
+#define GANQ_LUT_REGIME_DENSE256 7    /* ... 256-row tiles */
+int ganq_debug_lut_plan(int64_t M, int64_t m, int64_t n, int bits, int r, int outliers, int ncu, int* out, int out_len);
 /* prefill path: materialise Wq [m,n] = lut[o][index] in the activation dtype for a library GEMM */
 int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits, void* Wq_out,
                      void* stream);
@@ -278,7 +306,8 @@ int ganq_outlier_matmul(const void* x, int dtype, int64_t M, int64_t m, int64_t 
 /* ---- developer / test switches.  They are read from the environment (variable == option name) once, when the library
  * is loaded; afterwards only these calls change them -- the compute entry points never call getenv().  Options:
  * GANQ_T_FULL, GANQ_T_INCR_THR, GANQ_T_JACOBI, GANQ_SOLVE_ALL_ROWS, GANQ_MUPDATE_LDS, GANQ_WH_F64, GANQ_KMEANS_WCAP,
- * GANQ_CHOL_LOOKAHEAD, GANQ_ACCUM_DEBUG, GANQ_LUT_INWG, GANQ_LUT_WGS, GANQ_LUT_KS, GANQ_LUT_NT, GANQ_H_EXT, GANQ_SOLVE_VARIANT
+ * GANQ_CHOL_LOOKAHEAD, GANQ_ACCUM_DEBUG, GANQ_LUT_INWG, GANQ_LUT_WGS, GANQ_LUT_KS, GANQ_LUT_NT, GANQ_LUT_DENSE_M, GANQ_LUT_GEMM_RM,
+ * GANQ_LUT_GEMM_PIPE, GANQ_GEMM_H16_BM, GANQ_H_EXT, GANQ_SOLVE_VARIANT
  * (meanings: ganq_amd/csrc/runtime.hip).  None of them changes a result except where a test says so. */
 int ganq_debug_set_option(const char* name, long long value);
 int ganq_debug_get_option(const char* name, long long* value);

@@ -45,6 +45,11 @@ def check(y, x, Q, lut, bias, dtype, addend=None):
     (4, 512, torch.float16, 4096, 4096), (4, 2048, torch.bfloat16, 2048, 2048), (4, 1000, torch.float16, 129, 64),
     (4, 257, torch.float16, 8200, 512), (2, 96, torch.bfloat16, 64, 4096)])
 def test_lut_gemm_vs_dense(hip, bits, M, dtype, m, n):
+    """all of these take the fused LUT-dequant GEMM by shape (whole-K, split-K or pipelined), none the dense path: the one candidate,
+    (4, 2048, bf16, 2048, 2048), has 16 x 8 = 128 tiles of 128 x 256 on more CUs than that, which lut_dense_path() turns down -- asserted
+    through the plan query.  The dense path by shape: test_lut_gemm_baseline_shapes_vs_f_linear; forced at edge shapes:
+    tests/test_hip_lut_regimes.py"""
+    assert hip.debug_lut_plan(M, m, n, bits)["regime"] in ("gemm", "gemm_splitk", "gemm_pipe")
     Q, lut, x, bias = make(bits, M, m, n, dtype, bits * 1000 + M)
     qw = hip.pack_indices(Q, bits)
     check(hip.lut_linear(x, qw, lut, bias, bits), x, Q, lut, bias, dtype)
@@ -55,7 +60,15 @@ def test_lut_gemm_vs_dense(hip, bits, M, dtype, m, n):
 @pytest.mark.parametrize("m,n", [(4096, 4096), (14336, 4096)])
 def test_lut_gemm_baseline_shapes_vs_f_linear(hip, M, m, n):
     """the shapes VERDICT r02 item 6 names; besides the fp64 bound, the distance to the path it replaces
-    (dequantised weight + library fp16 GEMM) is of the order of one rounding"""
+    (dequantised weight + library fp16 GEMM) is of the order of one rounding.
+    By shape, M >= 1024 with at least a chip's worth of 128 x 256 tiles reaches "dequantise once + dense GEMM" (M in {2048, 4096} here,
+    on a 256-CU device); the others the fused kernel -- asserted through the plan query"""
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    dense = M >= 1024 and ((M + 127) // 128) * ((m + 255) // 256) >= ncu
+    regime = hip.debug_lut_plan(M, m, n, 4)["regime"]
+    assert (regime in ("dense128", "dense256")) == dense and (dense or regime in ("gemm", "gemm_splitk", "gemm_pipe")), regime
+    if ncu == 256:
+        assert dense == (M in (2048, 4096))
     Q, lut, x, bias = make(4, M, m, n, torch.float16, M + m)
     qw = hip.pack_indices(Q, 4)
     y = hip.lut_linear(x, qw, lut, bias, 4)

@@ -33,6 +33,7 @@ SIGNATURES = {
     "ganq_hip_selftest": (ctypes.c_int, [_c_vp]),
     "ganq_debug_div_check": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _c_vp, _c_vp, _c_vp]),
     "ganq_debug_wh_product": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "ganq_debug_t_sums": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [_c_vp] * 16),
     "ganq_debug_gemm_h16": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
     "ganq_hessian_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "ganq_hessian_accum": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_sz, _c_vp]),
@@ -245,6 +246,32 @@ def debug_wh_product(W, H):
     Hf = torch.empty((n, n), dtype=torch.float64, device=W.device)
     _call("ganq_debug_wh_product", (W, H, WH, Hf), W.data_ptr(), H.data_ptr(), m, n, WH.data_ptr(), Hf.data_ptr(), _ST)
     return WH, Hf
+
+
+def debug_t_sums(W, H, Qseq, V, rcond=-1.0):
+    """The fused loop's T-update on the index sequence Qseq [K,m,n] (uint8) and the integers behind it (ganq_debug_t_sums):
+    a dict of cuda tensors -- scale (fp64), ext, Hint / J [n,n] int32, hdiag_int / hdiag_j [n], F_hi / F_lo [K,m,16,16] int64,
+    chgcnt [K,m], Qprev [K,m,n] (None with GANQ_T_FULL=1), T_all [K,m,V], loss_rows_all [K,m], active_rows [K,m] /
+    active_count [K] (-1: no list built), full_ran [K]."""
+    W, H = _dev_f32(W, "W"), _dev_f32(H, "H")
+    if Qseq.dtype != torch.uint8 or not Qseq.is_cuda or Qseq.dim() != 3:
+        raise GanqHipError("Qseq must be a uint8 cuda tensor [K,m,n]")
+    Qseq = Qseq.contiguous()
+    K, m, n = Qseq.shape
+    if W.shape != (m, n) or H.shape != (n, n):
+        raise GanqHipError(f"shape mismatch W{tuple(W.shape)} H{tuple(H.shape)} Qseq{tuple(Qseq.shape)}")
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=W.device)  # noqa: E731
+    out = {"scale": new((), torch.float64), "ext": new((), torch.int32), "Hint": new((n, n), torch.int32),
+           "J": new((n, n), torch.int32), "hdiag_int": new((n,), torch.int32), "hdiag_j": new((n,), torch.int32),
+           "F_hi": new((K, m, 16, 16), torch.int64), "F_lo": new((K, m, 16, 16), torch.int64), "chgcnt": new((K, m), torch.int32),
+           "Qprev": None if debug_option_get("GANQ_T_FULL") == 1 else new((K, m, n), torch.uint8),
+           "T_all": new((K, m, V), torch.float32), "loss_rows_all": new((K, m), torch.float64),
+           "active_rows": new((K, m), torch.int32), "active_count": new((K,), torch.int32), "full_ran": new((K,), torch.int32)}
+    order = ("scale", "ext", "Hint", "J", "hdiag_int", "hdiag_j", "F_hi", "F_lo", "chgcnt", "Qprev", "T_all", "loss_rows_all",
+             "active_rows", "active_count", "full_ran")
+    _call("ganq_debug_t_sums", (W, H, Qseq), W.data_ptr(), H.data_ptr(), Qseq.data_ptr(), m, n, int(V), K, float(rcond),
+          *[_ptr(out[k]) for k in order], _ST)
+    return out
 
 
 def solve_s(W, L, T, want_err=False):

@@ -26,6 +26,7 @@
 #include <climits>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "update_t.h"
@@ -1613,6 +1614,126 @@ extern "C" int ganq_debug_wh_product(const float* W, const float* H, int64_t m, 
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e != hipSuccess) rc = fail(-4, "ganq_debug_wh_product: %s", hipGetErrorString(e));
     }
+    (void)hipFree(ws);
+    return rc;
+}
+
+namespace ganq {
+// No bucket sum reaches this value (|sum| <= n^2 2^30 <= 2^58 at n <= 16384): written into the first partial sum before an
+// iteration, it is still there afterwards exactly when the full accumulation did not run.
+constexpr long long T_FULL_PROBE = LLONG_MIN;
+
+__global__ __launch_bounds__(256) void jint_unbias_kernel(const short* __restrict__ Jint, int64_t total, int* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) out[i] = (int)Jint[i] - JBIAS;
+}
+__global__ void t_probe_set_kernel(long long* mpart) { mpart[0] = T_FULL_PROBE; }
+__global__ void t_probe_get_kernel(const long long* __restrict__ mpart, int* __restrict__ full_ran) {
+    *full_ran = mpart[0] != T_FULL_PROBE ? 1 : 0;
+}
+
+// body of ganq_debug_t_sums on its own scratch `ws` (layout lo) and codebook buffers Tc / Tn [m,V]
+static int debug_t_sums_run(const float* W, const float* H, const uint8_t* Qseq, int64_t m, int64_t n, int V, int K, double rcond,
+                            const TLayout& lo, char* ws, float* Tc, float* Tn, double* scale_out, int* ext_out, int* Hint_out,
+                            int* J_out, int* hdiag_int_out, int* hdiag_j_out, long long* F_hi, long long* F_lo, int* chgcnt_out,
+                            uint8_t* Qprev_out, float* T_all, double* loss_rows_all, int* active_rows, int* active_count,
+                            int* full_ran, hipStream_t stream) {
+    const size_t fbytes = (size_t)m * 256 * sizeof(long long);
+    long long* mpart = reinterpret_cast<long long*>(ws + lo.off_mpart);
+    long long* mpart_lo = reinterpret_cast<long long*>(ws + lo.off_mpart_lo);
+    // the sums of the extension word are not written when the extension is off: they read as zero then
+    GANQ_HIP_CHECK(hipMemsetAsync(mpart_lo, 0, (size_t)NP * fbytes, stream));
+    GANQ_HIP_CHECK(hipMemsetAsync(ws + lo.off_mstate_lo, 0, fbytes, stream));
+    GANQ_HIP_CHECK(hipMemsetAsync(Tc, 0, (size_t)m * V * sizeof(float), stream));
+    int rc = t_prepare(W, H, m, n, lo, ws, true, stream);
+    if (rc) return rc;
+    const TPrep* prep = reinterpret_cast<const TPrep*>(ws + lo.off_prep);
+    if (scale_out) GANQ_HIP_CHECK(hipMemcpyAsync(scale_out, &prep->scale, sizeof(double), hipMemcpyDeviceToDevice, stream));
+    if (ext_out) GANQ_HIP_CHECK(hipMemcpyAsync(ext_out, &prep->ext, sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (Hint_out)
+        GANQ_HIP_CHECK(hipMemcpyAsync(Hint_out, ws + lo.off_hint, (size_t)n * n * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (J_out)
+        hipLaunchKernelGGL(jint_unbias_kernel, dim3(1024), dim3(256), 0, stream, reinterpret_cast<const short*>(ws + lo.off_jint), n * n,
+                           J_out);
+    if (hdiag_int_out)
+        GANQ_HIP_CHECK(hipMemcpyAsync(hdiag_int_out, ws + lo.off_hdiag, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (hdiag_j_out)
+        GANQ_HIP_CHECK(hipMemcpyAsync(hdiag_j_out, ws + lo.off_hdiag_j, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    GANQ_LAUNCH_CHECK();
+    const bool stateful = opt_get(OPT_T_FULL) != 1;
+    for (int k = 0; k < K; ++k) {
+        const uint8_t* Q = Qseq + (size_t)k * m * n;
+        hipLaunchKernelGGL(t_probe_set_kernel, dim3(1), dim3(1), 0, stream, mpart);
+        // the driver's sequence (run_layer.hip): from the second iteration on only the changed rows are re-solved, in place
+        const bool in_place = k >= 1 && t_rows_listable(lo);
+        rc = t_iterate(Q, m, n, V, rcond, lo, ws, nullptr, in_place ? Tc : Tn, nullptr, nullptr, 1, nullptr, k, stream, in_place);
+        if (rc) return rc;
+        if (!in_place) std::swap(Tc, Tn);
+        if (full_ran) hipLaunchKernelGGL(t_probe_get_kernel, dim3(1), dim3(1), 0, stream, mpart, full_ran + k);
+        GANQ_LAUNCH_CHECK();
+        long long* fh = F_hi ? F_hi + (size_t)k * m * 256 : nullptr;
+        long long* fl = F_lo ? F_lo + (size_t)k * m * 256 : nullptr;
+        if (stateful) {
+            if (fh) GANQ_HIP_CHECK(hipMemcpyAsync(fh, ws + lo.off_mstate, fbytes, hipMemcpyDeviceToDevice, stream));
+            if (fl) GANQ_HIP_CHECK(hipMemcpyAsync(fl, ws + lo.off_mstate_lo, fbytes, hipMemcpyDeviceToDevice, stream));
+            if (Qprev_out)
+                GANQ_HIP_CHECK(hipMemcpyAsync(Qprev_out + (size_t)k * m * n, ws + lo.off_qprev, (size_t)m * n, hipMemcpyDeviceToDevice, stream));
+            if (chgcnt_out && k >= 1)
+                GANQ_HIP_CHECK(hipMemcpyAsync(chgcnt_out + (size_t)k * m, ws + lo.off_chgcnt, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, stream));
+        } else if (fh || fl) {
+            // the NP partial sums, summed and symmetrised by the loop's own reduction into a scratch copy of its outputs
+            long long* scratch_hi = reinterpret_cast<long long*>(ws + lo.off_mstate);
+            long long* scratch_lo = reinterpret_cast<long long*>(ws + lo.off_mstate_lo);
+            hipLaunchKernelGGL(m_reduce_kernel, dim3(1024 + 256), dim3(256), 0, stream, mpart, mpart_lo, (int)m, scratch_hi, scratch_lo,
+                               static_cast<const uint8_t*>(nullptr), static_cast<uint8_t*>(nullptr), (int64_t)0,
+                               static_cast<const long long*>(nullptr), 0ll, prep, 1024);
+            GANQ_LAUNCH_CHECK();
+            if (fh) GANQ_HIP_CHECK(hipMemcpyAsync(fh, scratch_hi, fbytes, hipMemcpyDeviceToDevice, stream));
+            if (fl) GANQ_HIP_CHECK(hipMemcpyAsync(fl, scratch_lo, fbytes, hipMemcpyDeviceToDevice, stream));
+        }
+        if (T_all) GANQ_HIP_CHECK(hipMemcpyAsync(T_all + (size_t)k * m * V, Tc, (size_t)m * V * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (loss_rows_all)
+            GANQ_HIP_CHECK(hipMemcpyAsync(loss_rows_all + (size_t)k * m, t_loss_rows(lo, ws), (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (in_place) {
+            const int* list = reinterpret_cast<const int*>(ws + lo.off_active);
+            if (active_rows)
+                GANQ_HIP_CHECK(hipMemcpyAsync(active_rows + (size_t)k * m, list, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, stream));
+            if (active_count) GANQ_HIP_CHECK(hipMemcpyAsync(active_count + k, list + m, sizeof(int), hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    GANQ_HIP_CHECK(hipStreamSynchronize(stream));
+    return 0;
+}
+}  // namespace ganq
+
+// developer check (tests): the loop's T-update on a given index sequence, with the integers behind it
+extern "C" int ganq_debug_t_sums(const float* W, const float* H, const uint8_t* Qseq, int64_t m, int64_t n, int V, int K, double rcond,
+                                 double* scale_out, int* ext_out, int* Hint_out, int* J_out, int* hdiag_int_out, int* hdiag_j_out,
+                                 long long* F_hi, long long* F_lo, int* chgcnt_out, uint8_t* Qprev_out, float* T_all,
+                                 double* loss_rows_all, int* active_rows, int* active_count, int* full_ran, void* stream_) {
+    if (m <= 0 || n <= 0 || K <= 0 || m > INT32_MAX / 2) return fail(-1, "ganq_debug_t_sums: bad shape / K");
+    if (n > 16384) return fail(-1, "ganq_debug_t_sums: n=%lld > 16384 not supported", (long long)n);
+    if (V < 2 || V > 16) return fail(-2, "ganq_debug_t_sums: V=%d not supported (bits 2..4 are implemented)", V);
+    if (!W || !H || !Qseq) return fail(-3, "ganq_debug_t_sums: null pointer");
+    if (rcond < 0) rcond = 1.1920928955078125e-07 * (double)V;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const TLayout lo = t_layout(m, n, true);
+    const size_t tbytes = align_up((size_t)m * V * sizeof(float), 256);
+    char* ws = nullptr;
+    GANQ_HIP_CHECK(hipMalloc(&ws, lo.total + 2 * tbytes));
+    // "no list was built" / "no change counts" read as -1 / 0
+    hipError_t e = hipSuccess;
+    if (active_rows) e = hipMemsetAsync(active_rows, 0xff, (size_t)K * m * sizeof(int), stream);
+    if (e == hipSuccess && active_count) e = hipMemsetAsync(active_count, 0xff, (size_t)K * sizeof(int), stream);
+    if (e == hipSuccess && chgcnt_out) e = hipMemsetAsync(chgcnt_out, 0, (size_t)K * m * sizeof(int), stream);
+    int rc = e == hipSuccess ? 0 : fail(-100, "ganq_debug_t_sums: %s", hipGetErrorString(e));
+    if (rc == 0)
+        rc = debug_t_sums_run(W, H, Qseq, m, n, V, K, rcond, lo, ws, reinterpret_cast<float*>(ws + lo.total),
+                              reinterpret_cast<float*>(ws + lo.total + tbytes), scale_out, ext_out, Hint_out, J_out, hdiag_int_out,
+                              hdiag_j_out, F_hi, F_lo, chgcnt_out, Qprev_out, T_all, loss_rows_all, active_rows, active_count, full_ran,
+                              stream);
+    else
+        (void)hipStreamSynchronize(stream);
+    if (rc != 0) (void)hipDeviceSynchronize();  // nothing of a failed run may still use the scratch
     (void)hipFree(ws);
     return rc;
 }

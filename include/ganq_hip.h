@@ -56,6 +56,27 @@ int ganq_debug_div_check(uint64_t count, uint32_t seed, unsigned long long* mism
  * 31-bit fixed-point H it is formed with.  Allocates its own scratch and synchronises the stream. */
 int ganq_debug_wh_product(const float* W, const float* H, int64_t m, int64_t n, double* WH_out, double* Hfixed_out, void* stream);
 
+/* Developer check (tests): the T-update of the fused loop on a GIVEN index sequence Qseq [K,m,n], with the integers behind it.
+ * Runs what ganq_run_layer runs per iteration (fixed-point conversion once, then K T-updates that keep the bucket sums between
+ * iterations, loss rows, changed rows re-solved in place from the second iteration on) under the current developer options; same
+ * limits (V in 2..16, n <= 16384).  Allocates its own scratch and synchronises the stream.  Outputs (device, each may be NULL):
+ *   after the conversion  scale (fp64), ext (int: the extension word is in use), Hint [n,n] / J [n,n] int32 with
+ *                         H ~= scale * (Hint + J / 65536) (J all zero without the extension), hdiag_int [n], hdiag_j [n];
+ *   after iteration k     F_hi / F_lo [K,m,16,16] int64: the bucket sums F[a][b] = sum_{u != v} [Q_u = a][Q_v = b] Hint[u][v] (resp. J)
+ *                         the per-row solve reads, without the diagonal term (F_lo all zero without the extension);
+ *                         chgcnt [K,m]: indices of the row that differ from iteration k - 1 (zeros for k = 0 and with GANQ_T_FULL=1);
+ *                         Qprev [K,m,n]: the indices the kept sums belong to (not written with GANQ_T_FULL=1);
+ *                         T_all [K,m,V], loss_rows_all [K,m] fp64;
+ *                         active_rows [K,m] / active_count [K]: the ascending list of changed rows the solve ran on and its length
+ *                         (all -1 where no list was built: k = 0, GANQ_T_FULL=1, GANQ_SOLVE_ALL_ROWS=1);
+ *                         full_ran [K]: 1 if the full accumulation produced the sums of iteration k, 0 if they were moved
+ *                         incrementally (read off a probe value the host puts into the partial sums, which only the full pass
+ *                         overwrites; no kernel is changed for it). */
+int ganq_debug_t_sums(const float* W, const float* H, const uint8_t* Qseq, int64_t m, int64_t n, int V, int K, double rcond,
+                      double* scale_out, int* ext_out, int* Hint_out, int* J_out, int* hdiag_int_out, int* hdiag_j_out,
+                      long long* F_hi, long long* F_lo, int* chgcnt_out, uint8_t* Qprev_out, float* T_all, double* loss_rows_all,
+                      int* active_rows, int* active_count, int* full_ran, void* stream);
+
 /* Developer / tests: the dense fp16 / bf16 GEMM the LUT forward uses from ~1024 rows of x on (csrc/gemm_h16.hip), on its own:
  * y [M,N] = x [M,K] @ w [N,K]^T (+ bias [N]) (+ addend [M,N] fp32), dtype 0 = fp16, 1 = bf16; K a multiple of 64, N of 4. */
 int ganq_debug_gemm_h16(const void* x, const void* w, const void* bias, const float* addend, int dtype, int64_t M, int64_t N,

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import t_update_model
 from conftest import rel_fro
 
 pytestmark = pytest.mark.gpu
@@ -75,6 +76,8 @@ def test_update_t_stage_wide_range_hessian(case, m, n, V):
     T, A, b = _lib.update_t(dev(WH), dev(H), dev(Q), V, want_ab=True)
     # A against the oracle's fp64 bucket sums of the fp32 entries, rounded to fp32 like the reference holds it
     assert rel_fro(A.cpu().numpy(), Ao) < 1e-6, case
+    # ... and bit for bit against the exact integer sums of the fixed point (tests/t_update_model.py)
+    assert t_update_model.bits_equal(A.cpu().numpy(), t_update_model.stage_A(H, Q, V)), case
     assert rel_fro(b.cpu().numpy(), bo) < 1e-6, case
     assert rel_fro(T.cpu().numpy(), To) < TOL_T, case
 

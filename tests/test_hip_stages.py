@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import t_update_model
 from conftest import golden_names, load_golden, rel_fro
 
 pytestmark = pytest.mark.gpu
@@ -316,6 +317,7 @@ def test_update_t_golden(hip, name):
     for k in range(int(g["K"])):
         T, A, b = hip.update_t(WH, H, dev(g["Q"][k]), V, want_ab=True)
         assert rel_fro(A.cpu().numpy(), g["A"][k]) < 1e-6
+        assert t_update_model.bits_equal(A.cpu().numpy(), t_update_model.stage_A(g["Xxt_damped"], g["Q"][k], V))  # exact integer sums
         assert rel_fro(b.cpu().numpy(), g["B"][k]) < 1e-6
         assert rel_fro(T.cpu().numpy(), g["T"][k + 1]) < TOL_T
 
@@ -328,6 +330,7 @@ def test_update_t_vs_oracle(hip, oracle, m, n, V, seed):
     To, Ao, bo = oracle.update_t(WH, H, Q, V, want_ab=True)
     T, A, b = hip.update_t(dev(WH), dev(H), dev(Q), V, want_ab=True)
     assert rel_fro(A.cpu().numpy(), Ao) < 1e-6
+    assert t_update_model.bits_equal(A.cpu().numpy(), t_update_model.stage_A(H, Q, V))  # exact integer sums (t_update_model.py)
     assert rel_fro(b.cpu().numpy(), bo) < 1e-6
     assert rel_fro(T.cpu().numpy(), To) < TOL_T
 

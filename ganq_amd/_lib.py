@@ -51,6 +51,7 @@ SIGNATURES = {
     "ganq_prologue_weights": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_kmeans_workspace_bytes": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "ganq_kmeans_init": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_debug_kmeans_plan": (ctypes.c_int, [_c_i64, _c_i64, ctypes.c_int, _c_vp]),
     "ganq_solve_s_workspace_bytes": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "ganq_solve_s": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp,
                                     _c_sz, _c_vp]),
@@ -628,6 +629,16 @@ def kmeans_init(W, col_weight, V: int):
     ws = _workspace(lib().ganq_kmeans_workspace_bytes(m, n, V), W.device)
     _call("ganq_kmeans_init", (W, cw, T0, ws), W.data_ptr(), _ptr(cw), m, n, V, T0.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
     return T0
+
+
+def debug_kmeans_plan(m: int, n: int, V: int) -> dict:
+    """what kmeans_init launches for W [m,n] under the current developer options (ganq_debug_kmeans_plan; host only, no GPU
+    needed).  resident: the LDS-resident kernel (else the windowed one); per_cu: workgroups per CU; qcap: queued ranges per balanced
+    level (resident); Wcap: the window in candidates (windowed); span: node spacing from which the windowed kernel may solve its
+    levels span by span (0: never)."""
+    out = (ctypes.c_int * 8)()
+    _check(lib().ganq_debug_kmeans_plan(int(m), int(n), int(V), ctypes.cast(out, _c_vp)), "ganq_debug_kmeans_plan")
+    return dict(resident=bool(out[0]), per_cu=out[1], P=out[2], qcap=out[3], Wcap=out[4], grid=out[5], lds_bytes=out[6], span=out[7])
 
 
 def pack_indices(Q, bits: int):

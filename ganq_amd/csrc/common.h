@@ -82,6 +82,7 @@ enum Opt : int {
     OPT_HESS_W4,
     OPT_KMEANS_SPAN,
     OPT_HESS_W4_WGS,
+    OPT_KMEANS_QCAP,
     OPT_COUNT
 };
 long long opt_get(int id);

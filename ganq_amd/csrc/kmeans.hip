@@ -2,7 +2,7 @@
 // which calls the un-vendored kmeans1d package; algorithm restated in oracle/ganq_oracle.c ganq_oracle_kmeans_row).
 //
 // One workgroup per row (persistent over rows):
-//   1. bitonic sort of (value, column) keys in LDS;
+//   1. bitonic sort of (value, column) keys in LDS; a row with at most V distinct values ends here: they are its codebook;
 //   2. weighted prefix sums cw, cwx, cwxx in fp64 (two-level: chunks of 16 summed left to right, chunk totals
 //      scanned left to right -- the same association order as the oracle);
 //   3. dynamic programme  D[k][i] = min_j D[k-1][j-1] + cost(j..i),  cost = sum w x^2 - (sum w x)^2 / sum w.
@@ -13,7 +13,7 @@
 //      argmin is also monotone in the number of clusters, opt[k-1][i] <= opt[k][i] (the cost is Monge), so the previous
 //      layer's argmin at the SAME position is a second lower bound -- it cuts the long ranges of the top levels, where a
 //      level costs its latency, by 3-10x and the candidates of a row by a fifth;
-//   4. backtrack, centroids = weighted means (ascending).
+//   4. backtrack, centroids = weighted means of the clusters' members, summed directly (ascending).
 #include "common.h"
 
 namespace ganq {
@@ -495,6 +495,75 @@ __device__ __forceinline__ void km_sort_row(const float* __restrict__ wrow, int 
     }
 }
 
+// Backtrack + centroids, both kernels.  Thread 0 walks the argmin table and leaves the cluster bounds in LDS (cluster k = sorted
+// positions bnd[k] .. bnd[k+1] - 1, the top one up to n - 1; an empty cluster -- fewer points than clusters -- has
+// bnd[k] == bnd[k+1]); then one wave per cluster sums w and w x over the cluster's OWN members.  Not a difference of the prefix sums: with weights over many decades a
+// light cluster behind a heavy prefix is below the rounding of cw / cwx there, and the quotient of two such differences is
+// noise (a centroid outside its cluster, a codebook out of order) -- the cost of a partition tolerates that error, a mean does not.
+// A non-negative weighted mean of its members, the centroid lies inside the cluster: ascending by construction.  A cluster
+// without weight takes its first value, an empty cluster repeats the next one above it (the top one is never empty).
+__device__ __forceinline__ void km_centroids(const uint16_t* arg, const double* xs, const double* wts, int n, int V, float* out,
+                                             uint16_t* bnd) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) {
+        int end = n - 1;
+        for (int k = V - 1; k >= 0; --k) {
+            int start = (end >= 0) ? arg[(size_t)k * n + end] : 0;
+            if (k == 0) start = 0;
+            bnd[k] = (uint16_t)start;
+            end = start - 1;
+        }
+    }
+    __syncthreads();
+    for (int k = tid >> 6; k < V; k += KL_THREADS / 64) {  // uniform per wave
+        const int s = bnd[k], e = (k + 1 < V) ? (int)bnd[k + 1] : n;
+        if (e <= s) continue;
+        double a = 0.0, b = 0.0;
+        for (int u = s + lane; u < e; u += 64) {
+            const double w = wts[u];
+            a += w;
+            b += w * xs[u];
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            a += __shfl_xor(a, off);
+            b += __shfl_xor(b, off);
+        }
+        if (lane == 0) {
+            const float c = (float)(a > 0.0 ? b / a : xs[s]);
+            out[k] = c;
+            for (int q = k - 1; q >= 0 && bnd[q] == s; --q) out[q] = c;  // the empty clusters below
+        }
+    }
+}
+
+// A row with at most V distinct values needs no dynamic programme: its optimum is 0, every value its own entry.  The DP cannot
+// be trusted with such a row -- the cost of two unlike values whose weights differ by 2^53 and more cancels to 0 in the prefix
+// sums, ties with the split, and the leftmost argmin merges them.  Counts the distinct values of the sorted row (xs, complete
+// behind a barrier; *dcount zeroed by thread 0 before the sort); if they fit, writes them ascending into the top of the codebook,
+// the smallest repeated below (what the backtrack leaves for empty clusters), and returns true (uniform).  `first` [256]: LDS.
+__device__ __forceinline__ bool km_few_values(const double* xs, int n, int V, float* out, uint16_t* first, int* dcount) {
+    const int tid = threadIdx.x;
+    for (int u = tid; u < n; u += KL_THREADS)
+        if (u == 0 || xs[u] != xs[u - 1]) {
+            const int slot = atomicAdd(dcount, 1);
+            if (slot < 256) first[slot] = (uint16_t)u;
+        }
+    __syncthreads();
+    const int D = *dcount;
+    if (D > V) return false;
+    if (tid < D) {
+        const int u = first[tid];
+        int rank = 0;
+        for (int e = 0; e < D; ++e) rank += (int)first[e] < u;
+        const float c = (float)xs[u];
+        out[V - D + rank] = c;
+        if (rank == 0)
+            for (int q = 0; q < V - D; ++q) out[q] = c;
+    }
+    __syncthreads();
+    return true;
+}
+
 // MINW = waves per SIMD the register allocation must allow: 4 (one workgroup per CU) or 8 (two, when two rows' arrays
 // fit the LDS together: n <= 2.3 k)
 template <int MINW>
@@ -514,6 +583,8 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_lds_kernel(const floa
     double* ctot = dprev;                                       // [3][nchunk] during the prefix sums only
     __shared__ double red_c[KL_THREADS / 64];
     __shared__ int red_j[KL_THREADS / 64];
+    __shared__ uint16_t bnd[256];  // first position of every cluster, left by the backtrack (V <= 256)
+    __shared__ int dcount;         // distinct values of the row
 
     const int tid = threadIdx.x;
     char* my = ws + (size_t)blockIdx.x * ws_stride;
@@ -528,6 +599,7 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_lds_kernel(const floa
         unsigned long long last_ = __builtin_amdgcn_s_memtime();
 #endif
         // ---- 1. sort ------------------------------------------------------------------------------
+        if (tid == 0) dcount = 0;
         km_sort_row(W + (int64_t)row * n, n, P, keys, tid);
         for (int u = tid; u < n; u += KL_THREADS) {
             const uint64_t key = keys[u];
@@ -537,6 +609,7 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_lds_kernel(const floa
             wts[u] = col_weight ? col_weight[(uint32_t)key] : 1.0;
         }
         __syncthreads();
+        if (km_few_values(xs, n, V, T0 + (int64_t)row * V, bnd, &dcount)) continue;
 
         KM_STAMP(0);
         // ---- 2. prefix sums (chunks of 16, then chunk totals, both left to right) ----------------------
@@ -696,22 +769,7 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_lds_kernel(const floa
 
         __syncthreads();  // the argmins of every layer (global) are complete before the backtrack reads them
         // ---- 4. backtrack + centroids ------------------------------------------------------------------------
-        if (tid == 0) {
-            int end = n - 1;
-            float* out = T0 + (int64_t)row * V;
-            for (int k = V - 1; k >= 0; --k) {
-                int start = (end >= 0) ? arg[(size_t)k * n + end] : 0;
-                if (k == 0) start = 0;
-                if (end >= start && end >= 0) {
-                    const double sw = cw[end + 1] - cw[start];
-                    const double swx = cwx[end + 1] - cwx[start];
-                    out[k] = (float)(sw > 0.0 ? swx / sw : xs[start]);
-                } else {
-                    out[k] = (k + 1 < V) ? out[k + 1] : (float)xs[n - 1];
-                }
-                end = start - 1;
-            }
-        }
+        km_centroids(arg, xs, wts, n, V, T0 + (int64_t)row * V, bnd);
         KM_STAMP(20);
         __syncthreads();
     }
@@ -736,6 +794,8 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_win_kernel(const floa
     double* ctot = reinterpret_cast<double*>(km_smem);         // [3][nchunk] during the prefix sums only
     __shared__ double red_c[KL_THREADS / 64];
     __shared__ int red_j[KL_THREADS / 64];
+    __shared__ uint16_t bnd[256];  // first position of every cluster, left by the backtrack (V <= 256)
+    __shared__ int dcount;         // distinct values of the row
 
     const int tid = threadIdx.x;
     const int n1 = n + 1;
@@ -752,6 +812,7 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_win_kernel(const floa
 
     for (int row = blockIdx.x; row < m; row += gridDim.x) {
         // ---- 1. sort ------------------------------------------------------------------------------
+        if (tid == 0) dcount = 0;
         km_sort_row(W + (int64_t)row * n, n, P, keys, tid);
         for (int u = tid; u < n; u += KL_THREADS) {
             const uint64_t key = keys[u];
@@ -761,6 +822,7 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_win_kernel(const floa
             wts[u] = col_weight ? col_weight[(uint32_t)key] : 1.0;
         }
         __syncthreads();
+        if (km_few_values(xs, n, V, T0 + (int64_t)row * V, bnd, &dcount)) continue;
 
         // ---- 2. prefix sums (chunks of 16, then chunk totals, both left to right) ----------------------
         for (int c = tid; c < nchunk; c += KL_THREADS) {
@@ -998,29 +1060,14 @@ __global__ __launch_bounds__(KL_THREADS, MINW) void kmeans_win_kernel(const floa
         }
 
         // ---- 4. backtrack + centroids ------------------------------------------------------------------------
-        if (tid == 0) {
-            int end = n - 1;
-            float* out = T0 + (int64_t)row * V;
-            for (int k = V - 1; k >= 0; --k) {
-                int start = (end >= 0) ? arg[(size_t)k * n + end] : 0;
-                if (k == 0) start = 0;
-                if (end >= start && end >= 0) {
-                    const double sw = cw[end + 1] - cw[start];
-                    const double swx = cwx[end + 1] - cwx[start];
-                    out[k] = (float)(sw > 0.0 ? swx / sw : xs[start]);
-                } else {
-                    out[k] = (k + 1 < V) ? out[k + 1] : (float)xs[n - 1];
-                }
-                end = start - 1;
-            }
-        }
+        km_centroids(arg, xs, wts, n, V, T0 + (int64_t)row * V, bnd);
         __syncthreads();
     }
 }
 
 struct KmPlan {
     bool lds;
-    int grid, P, Wcap, qcap = 0, per_cu = 1;
+    int grid, P, Wcap, qcap = 0, per_cu = 1, span_hs = 0;
     size_t smem, stride;
 };
 constexpr size_t KM_LDS_BUDGET = 160 * 1024 - 1024;  // dynamic part; the rest covers the static reduction slots
@@ -1047,6 +1094,10 @@ static KmPlan kmeans_plan(int64_t m, int64_t n, int V) {
         p.per_cu = per_cu;
         p.grid = (int)std::min<int64_t>(m, 256 * per_cu);
         p.stride = align_up(3 * (size_t)n * sizeof(double) + (size_t)V * (size_t)n * sizeof(uint16_t), 256);
+        // testing: a queue shorter than the plan's minimum, so that ordinary rows overflow it (the ranges beyond it are
+        // finished in place).  Only the capacity the kernel is told changes: LDS size and workgroups per CU stay
+        const int forced_q = (int)opt_get(OPT_KMEANS_QCAP);
+        if (forced_q >= 0) p.qcap = std::min(p.qcap, forced_q);
     } else {
         p.Wcap = (int)((KM_LDS_BUDGET - acur_bytes) / (4 * sizeof(double))) & ~63;
         // two workgroups per CU with half the window each, as long as the sort keys of a row (8 B x P) fit half the
@@ -1061,6 +1112,9 @@ static KmPlan kmeans_plan(int64_t m, int64_t n, int V) {
         p.smem = std::max((size_t)p.P * sizeof(uint64_t), 4 * (size_t)p.Wcap * sizeof(double) + acur_bytes);
         p.grid = (int)std::min<int64_t>(m, 256 * p.per_cu);
         p.stride = align_up((4 * (size_t)n + 3 * (size_t)(n + 1)) * sizeof(double) + (size_t)V * (size_t)n * sizeof(uint16_t), 256);
+        // levels with this spacing and below are solved span by span; GANQ_KMEANS_SPAN (developer): another power of two, 0 = never
+        p.span_hs = (int)opt_get(OPT_KMEANS_SPAN);
+        if (p.span_hs < 0) p.span_hs = KM_SPAN_HS;
     }
     return p;
 }
@@ -1075,12 +1129,34 @@ extern "C" size_t ganq_kmeans_workspace_bytes(int64_t m, int64_t n, int V) {
     return (size_t)p.grid * p.stride;
 }
 
+static int kmeans_check_shape(const char* who, int64_t m, int64_t n, int V) {
+    if (m < 0 || n < 0) return fail(-1, "%s: negative shape", who);
+    if (m == 0) return 0;
+    if (n < 1 || V < 1 || V > 256) return fail(-2, "%s: bad n=%lld / V=%d", who, (long long)n, V);
+    if (n > 16384) return fail(-2, "%s: n=%lld > 16384 not supported (LDS sort)", who, (long long)n);
+    return 0;
+}
+
+extern "C" int ganq_debug_kmeans_plan(int64_t m, int64_t n, int V, int* out) {
+    if (!out) return fail(-3, "ganq_debug_kmeans_plan: out must hold 8 ints");
+    if (m < 1) return fail(-1, "ganq_debug_kmeans_plan: bad shape");
+    if (int rc = kmeans_check_shape("ganq_debug_kmeans_plan", m, n, V)) return rc;
+    const KmPlan p = kmeans_plan(m, n, V);
+    out[0] = p.lds ? 1 : 0;
+    out[1] = p.per_cu;
+    out[2] = p.P;
+    out[3] = p.lds ? p.qcap : 0;
+    out[4] = p.Wcap;
+    out[5] = p.grid;
+    out[6] = (int)p.smem;
+    out[7] = p.span_hs;
+    return 0;
+}
+
 extern "C" int ganq_kmeans_init(const float* W, const double* col_weight, int64_t m, int64_t n, int V, float* T0,
                                 void* workspace, size_t workspace_bytes, void* stream_) {
-    if (m < 0 || n < 0) return fail(-1, "ganq_kmeans_init: negative shape");
+    if (int rc = kmeans_check_shape("ganq_kmeans_init", m, n, V)) return rc;
     if (m == 0) return 0;
-    if (n < 1 || V < 1 || V > 256) return fail(-2, "ganq_kmeans_init: bad n=%lld / V=%d", (long long)n, V);
-    if (n > 16384) return fail(-2, "ganq_kmeans_init: n=%lld > 16384 not supported (LDS sort)", (long long)n);
     if (!W || !T0) return fail(-3, "ganq_kmeans_init: null pointer");
     const KmPlan p = kmeans_plan(m, n, V);
     const size_t need = (size_t)p.grid * p.stride;
@@ -1099,9 +1175,7 @@ extern "C" int ganq_kmeans_init(const float* W, const double* col_weight, int64_
         if (rc) return rc;
     }
     ProfScope prof(KID_KMEANS, stream);
-    // (windowed kernel) levels with this spacing and below are solved span by span; GANQ_KMEANS_SPAN (developer): another power of two, 0 = never
-    int span_hs = (int)opt_get(OPT_KMEANS_SPAN);
-    if (span_hs < 0) span_hs = KM_SPAN_HS;
+    const int span_hs = p.span_hs;
     if (p.lds && p.per_cu >= 2)
         hipLaunchKernelGGL(kmeans_lds_kernel<8>, dim3(p.grid), dim3(KL_THREADS), p.smem, stream, W, col_weight, (int)m, (int)n, V,
                            p.P, p.qcap, T0, static_cast<char*>(workspace), p.stride);

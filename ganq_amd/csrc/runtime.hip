@@ -62,6 +62,7 @@ const OptDesc kOpts[OPT_COUNT] = {
     {"GANQ_HESS_W4", 1},           // Hessian, staged groups: 0 = never the transposed staging + 256 x 256 stream-K kernel (hessian_w4.hip); 2 = from 1024 in_features on (default: 3072)
     {"GANQ_KMEANS_SPAN", -1},      // windowed k-means: node spacing from which the levels are solved span by span (-1: default; 0: level by level as in rounds 1-3)
     {"GANQ_HESS_W4_WGS", 0},       // Hessian, staged groups (tests): cut the transposed path's launch for this many workgroups (0: one per CU)
+    {"GANQ_KMEANS_QCAP", -1},      // resident k-means (tests): at most this many queued ranges per balanced level, below the plan's minimum of 128 -- the others are finished in place (-1: off)
 };
 
 std::atomic<long long> g_opt[OPT_COUNT];

@@ -133,6 +133,12 @@ int ganq_cholesky(float* A, int64_t n, int64_t lda, int32_t* info, void* workspa
 size_t ganq_kmeans_workspace_bytes(int64_t m, int64_t n, int V);
 int ganq_kmeans_init(const float* W, const double* col_weight, int64_t m, int64_t n, int V, float* T0,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* what ganq_kmeans_init launches for this shape under the current developer options (host only, no GPU needed; the plan function
+ * the launch itself uses).  out[8] = { 1 LDS-resident kernel / 0 windowed kernel, workgroups per CU (1 or 2), P (power of two >= n),
+ * queue capacity of the balanced levels (resident), window in candidates (windowed; 0 resident), grid, dynamic LDS bytes,
+ * node spacing from which the windowed kernel may solve its levels span by span (0: never, and for the resident kernel) }.
+ * Same argument checks as ganq_kmeans_init: n > 16384 is the same error. */
+int ganq_debug_kmeans_plan(int64_t m, int64_t n, int V, int* out);
 
 /* ---- a4/a5: S-solve (ganq.py:533-565 torch branch == Metal kernel compute_s :39-270) --------
  * W [m,n], L [n,n] lower-triangular with leading dimension ldl, T [m,V].

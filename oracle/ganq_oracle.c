@@ -524,6 +524,26 @@ int ganq_oracle_kmeans_row(const float* w, const double* weights, int64_t n, int
         pairs[3 * u + 2] = (double)u;
     }
     qsort(pairs, (size_t)n, sizeof(double) * 3, cmp_pair);
+    /* at most V distinct values: the optimum is 0, every value its own entry, the smallest repeated below (what the
+     * backtrack leaves for empty clusters).  The programme below cannot be trusted with such a row: the cost of two unlike
+     * values whose weights differ by 2^53 and more cancels to 0 in the prefix sums and ties with the split */
+    {
+        int64_t D = 0;
+        for (int64_t u = 0; u < n && D <= V; ++u)
+            if (u == 0 || pairs[3 * u] != pairs[3 * (u - 1)]) ++D;
+        if (D <= V) {
+            int64_t k = V - D - 1;
+            for (int64_t u = 0; u < n; ++u)
+                if (u == 0 || pairs[3 * u] != pairs[3 * (u - 1)]) centroids[++k] = (float)pairs[3 * u];
+            for (int64_t q = 0; q < V - D; ++q) centroids[q] = (float)pairs[0];
+            free(pairs);
+            free(pre);
+            free(D0);
+            free(D1);
+            free(arg);
+            return 0;
+        }
+    }
     double* cw = pre;
     double* cwx = pre + (n + 1);
     double* cwxx = pre + 2 * (n + 1);
@@ -576,7 +596,13 @@ int ganq_oracle_kmeans_row(const float* w, const double* weights, int64_t n, int
         int64_t start = (end >= 0) ? arg[(size_t)k * n + end] : 0;
         if (k == 0) start = 0;
         if (end >= start && end >= 0) {
-            double sw = cw[end + 1] - cw[start], swx = cwx[end + 1] - cwx[start];
+            /* summed over the cluster's own members, not taken as a difference of the prefix sums: with weights over
+             * many decades a light cluster behind a heavy prefix is below the rounding of the prefix sums there */
+            double sw = 0.0, swx = 0.0;
+            for (int64_t u = start; u <= end; ++u) {
+                sw += pairs[3 * u + 1];
+                swx += pairs[3 * u + 1] * pairs[3 * u];
+            }
             centroids[k] = (float)(sw > 0.0 ? swx / sw : pairs[3 * start]);
         } else {
             /* empty cluster: repeat the neighbouring value (cannot happen with >= V distinct points) */

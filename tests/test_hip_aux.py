@@ -251,6 +251,12 @@ def test_cholesky_not_positive_definite_raises(hip):
 
 
 # ------------------------------------------------------------------------------------------ k-means
+def row_max_err(T0, ref):
+    """largest error of any row, relative to that row's largest entry (a norm over the matrix dilutes one wrong row)"""
+    scale = np.maximum(np.abs(ref).max(axis=1), np.finfo(np.float32).tiny)
+    return float((np.abs(T0.astype(np.float64) - ref).max(axis=1) / scale).max())
+
+
 @pytest.mark.parametrize("m,n,V,seed", [(8, 64, 4, 1), (32, 300, 16, 2), (16, 1024, 8, 3), (5, 4096, 16, 4), (3, 17, 16, 5),
                                         (700, 256, 16, 6), (2, 4700, 16, 7), (2, 4800, 16, 8), (3, 1, 4, 9), (2, 2, 4, 10),
                                         # every CU busy (one / two workgroups per CU): the ordering bugs of a workgroup-wide sort or
@@ -262,7 +268,7 @@ def test_kmeans_vs_oracle(hip, oracle, m, n, V, seed):
     wts = rng.uniform(0.2, 3.0, n) ** -4
     T0 = hip.kmeans_init(dev(W), torch.from_numpy(wts), V).cpu().numpy()
     ref = oracle.kmeans_init(W, wts, V)
-    assert rel_fro(T0, ref) < 1e-6, np.abs(T0 - ref).max()
+    assert row_max_err(T0, ref) < 1e-6, np.abs(T0 - ref).max()
     assert np.all(np.diff(T0, axis=1) >= 0)
 
 
@@ -277,7 +283,7 @@ def test_kmeans_windowed_kernel_small_windows(hip, oracle, wcap, lib_options):
         wts = rng.uniform(0.2, 3.0, n) ** -4
         T0 = hip.kmeans_init(dev(W), torch.from_numpy(wts), V).cpu().numpy()
         ref = oracle.kmeans_init(W, wts, V)
-        assert rel_fro(T0, ref) < 1e-6, (m, n, V, np.abs(T0 - ref).max())
+        assert row_max_err(T0, ref) < 1e-6, (m, n, V, np.abs(T0 - ref).max())
 
 
 def test_kmeans_golden_T0(hip):

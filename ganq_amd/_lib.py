@@ -98,6 +98,7 @@ SIGNATURES = {
                                                _c_sz, _c_vp]),
     "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
+    "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_cutoffs": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_extract": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_matmul": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -669,6 +670,35 @@ def lut_dequant(qweight, lut, n: int, bits: int):
     Wq = torch.empty((m, n), dtype=lut.dtype, device=lut.device)
     _call("ganq_lut_dequant", (qweight, lut, Wq), qweight.data_ptr(), lut.data_ptr(), code, m, n, bits, Wq.data_ptr(), _ST)
     return Wq
+
+
+def lut_embedding(ids, qweight, lut, in_features: int, bits: int, outliers=None, out=None):
+    """rows of the dequantised LUT weight by id: ids int64 (any shape), qweight int32 [n*bits/32, m], lut [m, V] fp16 / bf16 ->
+    [..., n] in lut's dtype; outliers: (rowptr, cols, vals in lut's dtype) of the layer, added with one rounding.  An id outside
+    [0, m) gives a row of zeros.  One launch, nothing else: capturable in a HIP graph (pass `out` to keep the address fixed)."""
+    code = _act_dtype(lut, "lut")
+    if ids.dtype != torch.int64 or not ids.is_cuda:
+        raise GanqHipError("lut_embedding: ids must be an int64 cuda tensor")
+    if qweight.dtype != torch.int32:
+        raise GanqHipError("lut_embedding: qweight must be int32")
+    ids, qweight, lut = ids.contiguous(), qweight.contiguous(), lut.contiguous()
+    m, n = lut.shape[0], int(in_features)
+    if tuple(qweight.shape) != (n * bits // 32, m) or lut.shape[1] != 2 ** bits:
+        raise GanqHipError(f"lut_embedding: qweight {tuple(qweight.shape)} / lut {tuple(lut.shape)} do not fit [{m}, {n}] at {bits} bits")
+    rowptr = cols = vals = None
+    if outliers is not None:
+        rowptr, cols, vals = outliers
+        if vals.dtype != lut.dtype or rowptr.dtype != torch.int32 or cols.dtype != torch.int32 or rowptr.numel() != m + 1:
+            raise GanqHipError("lut_embedding: outlier vals must have lut's dtype, rowptr [m + 1] / cols must be int32")
+    N = ids.numel()
+    if out is None:
+        out = torch.empty(tuple(ids.shape) + (n,), dtype=lut.dtype, device=lut.device)
+    elif out.dtype != lut.dtype or out.numel() != N * n or not out.is_contiguous():
+        raise GanqHipError("lut_embedding: out must be contiguous, of lut's dtype, with ids.numel() * in_features elements")
+    _call("ganq_lut_embedding", (ids, qweight, lut, rowptr, cols, vals, out), ids.data_ptr(), N, qweight.data_ptr(), lut.data_ptr(), code, m, n,
+          bits, _ptr(rowptr), _ptr(cols) if cols is not None and cols.numel() else None,
+          _ptr(vals) if vals is not None and vals.numel() else None, out.data_ptr(), _ST)
+    return out
 
 
 LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*

@@ -110,7 +110,7 @@ class GPTQProcessor:
     def results(self):
         return self._results
 
-    def finalize(self, model: nn.Module, backend=None, **kwargs):
+    def finalize(self, model: nn.Module, backend=None, lm_head_name=None, **kwargs):
         """FORMAT.GANQ_LUT: replace every quantized nn.Linear by a packed QuantLinear, through the same steps as the
         reference's pack path (pack_model -> make_quant -> select_quant_linear -> create_quant_layer -> pack_module,
         utils/model.py:573-639): ganq_amd/nn_modules/backend.py.  FORMAT.FAKE: the dequantised weights already sit in
@@ -118,5 +118,5 @@ class GPTQProcessor:
         from ..nn_modules.backend import BACKEND, pack_model
 
         packable = {k: v for k, v in self._results.items() if v.get("packable", True)}
-        pack_model(model, quant_result=packable, qcfg=self.qcfg, backend=backend or BACKEND.AUTO)
+        pack_model(model, quant_result=packable, qcfg=self.qcfg, backend=backend or BACKEND.AUTO, lm_head_name=lm_head_name)
         return model

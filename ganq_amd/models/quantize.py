@@ -9,11 +9,15 @@ save/load       the packed format the reference lacks: it can only save FORMAT.F
                    tensor of the model unchanged; `quantize_config.json` next to it with the per-module bit widths.
                    A layer with an adapter adds `<name>.lora_A` fp16 [r, in] / `<name>.lora_B` fp16 [out, r] to the same
                    file and `"adapter_rank": r` to its entry of `"modules"` (absent in older checkpoints: no adapter).
+                   With `QuantizeConfig.lm_head` the output head is one more entry of `"modules"`; an input embedding served from the
+                   packed head (`ganq_tied_embedding="share"`) has no tensor in the file and is recorded as
+                   `"tied_embedding": {"module": <embedding>, "source": <head>}` (absent in older checkpoints: nothing shared).
 gptq_style_ppl  the evaluator behind the README numbers (examples/quantization/basic_usage_wikitext2.py:63-93):
                    non-overlapping windows of `seqlen` tokens, mean token NLL, exp.
 """
 import json
 import os
+import time
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -21,8 +25,9 @@ import torch.nn as nn
 
 from ..looper.gptq_processor import GPTQProcessor
 from ..looper.module_looper import ModuleLooper
+from ..looper.named_module import NamedModule
 from ..adapter import Lora
-from ..nn_modules.qlinear.ganq_hip import GanqHipQuantLinear
+from ..nn_modules.qlinear.ganq_hip import GanqHipQuantEmbedding, GanqHipQuantLinear
 from ..quantization.config import FORMAT, QuantizeConfig
 from .definitions import LayerMap, layer_map_for
 
@@ -61,11 +66,94 @@ def capture_layer_inputs(model: nn.Module, layers: Sequence[nn.Module], batches:
     return hidden, kwargs_list
 
 
+def _set_module(root: nn.Module, path: str, new: nn.Module) -> None:
+    parent, _, child = path.rpartition(".")
+    setattr(_get_module(root, parent) if parent else root, child, new)
+
+
+def _name_of(model: nn.Module, module: nn.Module) -> str:
+    for name, mod in model.named_modules():
+        if mod is module:
+            return name
+    raise ValueError(f"{type(module).__name__} is not a module of the model")
+
+
+class _Head:
+    """the output head of a model and its tie to the input embedding, as the head stage of quantize_model needs them"""
+
+    def __init__(self, model: nn.Module, qcfg: QuantizeConfig):
+        get = getattr(model, "get_output_embeddings", None)
+        self.module = get() if get is not None else None
+        if self.module is None:
+            raise ValueError("QuantizeConfig.lm_head: the model has no output embeddings (get_output_embeddings())")
+        if not isinstance(self.module, nn.Linear):
+            raise NotImplementedError(f"QuantizeConfig.lm_head: the head is a {type(self.module).__name__}, only nn.Linear is quantized")
+        self.name = _name_of(model, self.module)
+        self.skipped = qcfg.dynamic_get(layer_name=self.name) is False  # '-:' pattern
+        get = getattr(model, "get_input_embeddings", None)
+        self.embedding = get() if get is not None else None
+        w = getattr(self.embedding, "weight", None)
+        self.tied = w is not None and (w is self.module.weight or w.data_ptr() == self.module.weight.data_ptr())
+        self.embedding_name = _name_of(model, self.embedding) if self.tied else None
+        self.share = self.tied and not self.skipped and qcfg.ganq_tied_embedding == "share"
+        if self.share:  # refuse before any work is done
+            if type(self.embedding) is not nn.Embedding:
+                raise NotImplementedError(f"ganq_tied_embedding=`share`: the input embedding is a {type(self.embedding).__name__}; only "
+                                          f"a plain nn.Embedding is a row lookup of the head's table (use `untie`)")
+            if qcfg.format == FORMAT.GANQ_LUT and w.dtype not in (torch.float16, torch.bfloat16):
+                raise NotImplementedError(f"ganq_tied_embedding=`share`: a {w.dtype} table cannot be served from the packed head "
+                                          f"(float16 and bfloat16 can; use `untie`)")
+        self.table_dtype = w.dtype if self.tied else None
+
+    def break_tie(self, model: nn.Module, qcfg: QuantizeConfig) -> None:
+        """before the head is quantized: GPTQProcessor.process writes the head's weight, which a tied embedding would share"""
+        if not self.tied:
+            return
+        if not self.share:
+            w = self.module.weight
+            self.embedding.weight = nn.Parameter(w.detach().clone(), requires_grad=w.requires_grad)
+        # ("share": FORMAT.FAKE keeps the one Parameter, so the embedding's weight IS the dequantised head weight; FORMAT.GANQ_LUT
+        # replaces the embedding after packing)
+        cfg = getattr(model, "config", None)
+        if cfg is not None and getattr(cfg, "tie_word_embeddings", False):
+            cfg.tie_word_embeddings = False  # tie_weights() must not hang a `weight` onto the packed head
+
+    def share_packed(self, model: nn.Module) -> None:
+        head_q = _get_module(model, self.name)
+        if self.share and isinstance(head_q, GanqHipQuantLinear):
+            _set_module(model, self.embedding_name, GanqHipQuantEmbedding(head_q, dtype=self.table_dtype,
+                                                                          padding_idx=self.embedding.padding_idx))
+
+
+def _quantize_head(proc: GPTQProcessor, model: nn.Module, lm: LayerMap, head: _Head, hidden, layer_index: int, progress=None):
+    """the head as one one-module group of the same processor, under its real module name, on `pre_head` of the hidden states
+    leaving the last decoder layer (the looper's outputs: what the quantized body feeds it)"""
+    pre = [m for m in (_get_module(model, p) for p in lm.pre_head) if m is not None]
+    named = NamedModule(head.module, name=head.name, full_name=head.name, layer_index=layer_index)
+    proc.preprocess(named, buffered_fwd=False)
+    if proc.is_skipped(named):
+        return
+    hook = proc.preprocess_fwd_hook(head.name)
+    for x in hidden:
+        for mod in pre:
+            x = mod(x)
+        hook(head.module, (x,), None)  # the statistics hook alone: the logits of the calibration batches are not needed
+    task = proc.tasks[head.name]
+    end = getattr(task, "end_of_calibration", None)
+    if end is not None:
+        end()
+    proc.process(named)
+    if progress:
+        progress(named)
+
+
 @torch.no_grad()
 def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: QuantizeConfig,
                    layer_map: Optional[LayerMap] = None, progress=None, processor: Optional[GPTQProcessor] = None,
                    **looper_options) -> GPTQProcessor:
-    """Quantize every Linear the layer map names, layer by layer, on the device the model lives on.  `calibration`:
+    """Quantize every Linear the layer map names, layer by layer, on the device the model lives on (with `qcfg.lm_head` also the
+    output head, last, on the normalised hidden states the quantized body produces; a tied input embedding follows
+    `qcfg.ganq_tied_embedding`).  `calibration`:
     token-id tensors [b, seq].  Returns the processor (per-module log, results); the model is modified in place
     (GanqHipQuantLinear modules for FORMAT.GANQ_LUT, dequantised nn.Linear weights for FORMAT.FAKE).
     looper_options: `early_exit=` / `cache_outputs=` / `share_group_hessian=` of ModuleLooper (results do not depend on
@@ -82,6 +170,14 @@ def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: 
     if qcfg.adapter is not None and dist.world > 1:
         raise NotImplementedError("QuantizeConfig.adapter with several ranks: the row shards would have to exchange the "
                                   "quantization error (and the layer mode the adapters); quantize on one GPU")
+    head = None
+    if qcfg.lm_head:
+        if dist.world > 1:
+            raise NotImplementedError("QuantizeConfig.lm_head with several ranks: the head's rows would have to be sharded like the "
+                                      "body's and its calibration inputs gathered; quantize on one GPU")
+        head = _Head(model, qcfg)
+        if head.skipped:
+            head = None
     batches = [b.to(dev) for b in (calibration[dist.rank::dist.world] if local else calibration)]
     was_training = model.training
     model.eval()
@@ -92,9 +188,21 @@ def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: 
     def fwd(layer, x, kw):
         return layer(x, **kw)
 
-    ModuleLooper(proc, layers, lm.layer_modules, layers_prefix=lm.layers_node, **looper_options).loop(
+    hidden = ModuleLooper(proc, layers, lm.layer_modules, layers_prefix=lm.layers_node, **looper_options).loop(
         hidden, kwargs_list, forward=fwd, progress=progress, inputs_are_local=local)
-    proc.finalize(model)
+    if head is not None:
+        if dev.type == "cuda":  # (once per model: the stage's seconds are reported, so they should be the stage's)
+            torch.cuda.synchronize(dev)
+        t0 = time.time()
+        head.break_tie(model, qcfg)
+        _quantize_head(proc, model, lm, head, hidden, len(layers), progress)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        proc.head_stage_seconds = time.time() - t0
+    del hidden
+    proc.finalize(model, lm_head_name=head.name if head is not None else None)
+    if head is not None:
+        head.share_packed(model)
     model.quantize_config = qcfg
     model.train(was_training)
     return proc
@@ -126,20 +234,29 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
     save_file(out, os.path.join(path, "model.safetensors"), metadata={"format": "pt", "ganq_format": FORMAT.GANQ_LUT})
     cfg = qcfg.to_dict()
     cfg["modules"] = modules
+    for n, m in model.named_modules():  # an embedding served from the packed head: the checkpoint holds no table for it
+        if isinstance(m, GanqHipQuantEmbedding):
+            cfg["tied_embedding"] = {"module": n, "source": _name_of(model, m.head)}
     with open(os.path.join(path, "quantize_config.json"), "w") as f:
         json.dump(cfg, f, indent=2, default=str)
 
 
 def load_quantized(model: nn.Module, path: str) -> nn.Module:
     """`model`: a freshly constructed (unquantized, any weights) instance of the same architecture.  Replaces the
-    recorded Linear modules by GanqHipQuantLinear, then loads every tensor of the checkpoint."""
+    recorded Linear modules by GanqHipQuantLinear (the output head among them if it was quantized; an embedding recorded as
+    `"tied_embedding"` by a GanqHipQuantEmbedding on the rebuilt head), then loads every tensor of the checkpoint."""
     from safetensors.torch import load_file
 
     with open(os.path.join(path, "quantize_config.json")) as f:
         cfg = json.load(f)
     modules: Dict[str, dict] = cfg.pop("modules")
+    tied = cfg.pop("tied_embedding", None)
     qcfg = QuantizeConfig.from_dict(cfg)
     named = dict(model.named_modules())
+    get_head = getattr(model, "get_output_embeddings", None)
+    head = get_head() if get_head is not None else None
+    head_packed = head is not None and any(named[n] is head for n in modules)
+    table_dtype = named[tied["module"]].weight.dtype if tied else None
     for name, info in modules.items():
         lin = named[name]
         q = GanqHipQuantLinear(bits=info["bits"], group_size=qcfg.group_size, sym=qcfg.sym, desc_act=qcfg.desc_act,
@@ -148,6 +265,12 @@ def load_quantized(model: nn.Module, path: str) -> nn.Module:
                                adapter=Lora(rank=info["adapter_rank"]) if info.get("adapter_rank") else None).to(lin.weight.device)
         parent, _, child = name.rpartition(".")
         setattr(named[parent] if parent else model, child, q)
+    if tied:  # the shared embedding reads the rebuilt head: no table of its own is expected in the checkpoint
+        emb = named[tied["module"]]
+        _set_module(model, tied["module"], GanqHipQuantEmbedding(_get_module(model, tied["source"]), dtype=table_dtype,
+                                                                 padding_idx=getattr(emb, "padding_idx", None)))
+    if head_packed and getattr(getattr(model, "config", None), "tie_word_embeddings", False):
+        model.config.tie_word_embeddings = False  # a packed head has no `weight`: tie_weights() below must not re-tie it
     state = load_file(os.path.join(path, "model.safetensors"))
     missing, unexpected = model.load_state_dict(state, strict=False)
     missing = [k for k in missing if k not in ("lm_head.weight",)]  # tied to the embeddings

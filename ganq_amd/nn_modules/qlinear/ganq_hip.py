@@ -314,4 +314,63 @@ class _GanqLutLinearFn(torch.autograd.Function):
         return dx, dlut, None
 
 
-__all__ = ["GanqHipQuantLinear", "BACKEND_GANQ_HIP"]
+class GanqHipQuantEmbedding(nn.Module):
+    """The input embedding of a model whose embedding table is tied to a quantized output head (`QuantizeConfig.lm_head` with
+    `ganq_tied_embedding="share"`): `forward(ids)` is row `id` of `head.dequantize_weight()`, gathered out of the head's packed
+    stream by one HIP launch (csrc/lut_embedding.hip).  The head's outliers are part of the row; its adapter is not -- an adapter
+    corrects the head's OUTPUT under the head's inputs and has no meaning for a lookup.
+
+    The module owns no tensor: it keeps an unregistered reference to the head and reads `qweight`, `lut` and the outlier CSR when it
+    is called, so `state_dict()` gains no key, `.to()` of the model moves everything once and a checkpoint holds one table.  Ids of
+    any shape give `[..., in_features]` in `dtype` (the dtype of the table this module replaced: fp16 or bf16); an id outside the
+    vocabulary gives a row of zeros.  No gradient flows through it: the output never has a grad_fn, neither the indices nor the
+    codebook are trained through the lookup."""
+
+    def __init__(self, head: GanqHipQuantLinear, dtype: torch.dtype = torch.float16, padding_idx=None):
+        super().__init__()
+        if not isinstance(head, GanqHipQuantLinear):
+            raise TypeError(f"GanqHipQuantEmbedding reads a GanqHipQuantLinear, got {type(head).__name__}")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"GanqHipQuantEmbedding: a table of {dtype} cannot be shared with the packed head "
+                                      f"(float16 and bfloat16 can)")
+        object.__setattr__(self, "_head", head)  # not a submodule: nothing of the head is registered twice
+        self.num_embeddings, self.embedding_dim = head.out_features, head.in_features
+        self.dtype = dtype
+        self.padding_idx = padding_idx  # (nn.Embedding's forward does not read it either: it only masks the gradient)
+
+    @property
+    def head(self) -> GanqHipQuantLinear:
+        return self._head
+
+    def _as_dtype(self, slot: str, t: torch.Tensor) -> torch.Tensor:
+        """`t` in the output dtype: the buffer itself when it has it, else a copy converted once and kept until the buffer is
+        replaced or written in place (like GanqHipQuantLinear._lora_as)"""
+        t = t.detach()
+        if t.dtype == self.dtype:
+            return t
+        key = (self.dtype, t.data_ptr(), t._version)
+        cache = self.__dict__.get(slot)
+        if cache is None or cache[0] != key:
+            cache = (key, t.to(self.dtype).contiguous())
+            object.__setattr__(self, slot, cache)
+        return cache[1]
+
+    @torch.no_grad()
+    def forward(self, ids: torch.Tensor):
+        head = self._head
+        if not ids.is_cuda:
+            raise _lib.GanqHipError("GanqHipQuantEmbedding runs on the GPU only (no CPU fallback)")
+        if ids.dtype != torch.int64:
+            if ids.is_floating_point() or ids.dtype == torch.bool:
+                raise TypeError(f"GanqHipQuantEmbedding: ids must be integers, got {ids.dtype}")
+            ids = ids.long()
+        outl = None
+        if head.outliers:
+            outl = (head.outlier_rowptr, head.outlier_cols, self._as_dtype("_vals_cache", head.outlier_vals))
+        return _lib.lut_embedding(ids, head.qweight, self._as_dtype("_lut_cache", head.lut), head.in_features, head.bits, outliers=outl)
+
+    def extra_repr(self) -> str:
+        return f"{self.num_embeddings}, {self.embedding_dim}, bits={self._head.bits}, dtype={self.dtype}"
+
+
+__all__ = ["GanqHipQuantLinear", "GanqHipQuantEmbedding", "BACKEND_GANQ_HIP"]

@@ -84,6 +84,12 @@ class QuantizeConfig:
     # reference field (config.py `adapter`): a Lora (or {"name": "lora", "rank": r}) -> every packed module gets a training-free
     # EoRA adapter of rank r, generated right after its quantization.  Rank: a positive multiple of 16, at most 256.
     adapter: Optional[Union[Dict[str, Any], Lora]] = field(default=None)
+    # not in the reference (which refuses lm_head=True on a model whose head is tied to the input embedding,
+    # module_looper.py:131-136): what becomes of the embedding when the tied head is quantized.  "untie": the embedding keeps
+    # its own copy of the original table (fp16 nn.Embedding).  "share": the embedding reads rows out of the head's packed table
+    # (GanqHipQuantEmbedding; no second table in memory or in the checkpoint -- the body was calibrated on the exact embedding,
+    # so it never saw the embedding's quantization error).  Without a tie the field has no effect.
+    ganq_tied_embedding: str = field(default="untie", metadata={"choices": ["untie", "share"]})
 
     def __post_init__(self):
         info = fields(self)
@@ -138,6 +144,8 @@ class QuantizeConfig:
             raise ValueError(f"QuantizeConfig: unknown `act_sort`: {self.act_sort}")
         if self.l_damp_style not in ["gptq", "ganq"]:
             raise ValueError(f"QuantizeConfig: unknown `l_damp_style`: {self.l_damp_style}")
+        if self.ganq_tied_embedding not in ["untie", "share"]:
+            raise ValueError(f"QuantizeConfig: unknown `ganq_tied_embedding`: {self.ganq_tied_embedding}")
         if self.dead not in ["zero", "mean"]:
             raise ValueError(f"QuantizeConfig: unknown `dead`: {self.dead}")
         if self.meta is None:

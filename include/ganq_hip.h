@@ -291,6 +291,15 @@ int ganq_debug_lut_plan(int64_t M, int64_t m, int64_t n, int bits, int r, int ou
 int ganq_lut_dequant(const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n, int bits, void* Wq_out,
                      void* stream);
 
+/* embedding lookup out of the packed stream of a LUT layer (a model whose input embedding shares the quantized head's table):
+ *   out [N, n] (dtype 0 = fp16, 1 = bf16; 16-byte aligned) row t = lut[id][Q[id][:]] (+ the CSR entries of row id, ONE rounded add in
+ *   dtype per element, as Wq + W_sparse), id = ids[t]; an id outside [0, m) gives a row of zeros and reads nothing.
+ * qweight / lut / the CSR by output feature (vals in dtype) as ganq_lut_linear_fwd_outliers takes them; the three outlier pointers
+ * may be NULL (no outliers: no add).  No workspace, no host synchronisation, no allocation: one launch, capturable in a HIP graph. */
+int ganq_lut_embedding(const int64_t* ids, int64_t N, const int32_t* qweight, const void* lut, int dtype, int64_t m, int64_t n,
+                       int bits, const int32_t* outlier_rowptr, const int32_t* outlier_cols, const void* outlier_vals, void* out,
+                       void* stream);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,

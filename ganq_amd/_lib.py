@@ -53,6 +53,8 @@ SIGNATURES = {
     "ganq_kmeans_init": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_sz, _c_vp]),
     "ganq_debug_kmeans_plan": (ctypes.c_int, [_c_i64, _c_i64, ctypes.c_int, _c_vp]),
     "ganq_solve_s_workspace_bytes": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
+    "ganq_debug_solve_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
+    "ganq_debug_solve_role": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "ganq_solve_s": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp,
                                     _c_sz, _c_vp]),
     "ganq_matmul_f32": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
@@ -699,6 +701,27 @@ def lut_embedding(ids, qweight, lut, in_features: int, bits: int, outliers=None,
           bits, _ptr(rowptr), _ptr(cols) if cols is not None and cols.numel() else None,
           _ptr(vals) if vals is not None and vals.numel() else None, out.data_ptr(), _ST)
     return out
+
+
+SOLVE_REGIMES = ("none", "shared", "duo", "trio")  # GANQ_SOLVE_PLAN_*
+
+
+def debug_solve_plan(active_tiles: int, grid: int = 0, ncu: int = 0) -> dict:
+    """which helper workgroups an S-solve launch with `active_tiles` 16-row tiles still to solve gets under the current developer
+    options (ganq_debug_solve_plan: the function the kernel evaluates).  grid 0: what the host launches for a layer of that many
+    tiles; ncu > 0: plan for that many compute units, no GPU needed; 0: those of the current device."""
+    out = (ctypes.c_int * 4)()
+    _check(lib().ganq_debug_solve_plan(int(active_tiles), int(grid), int(ncu), ctypes.cast(out, _c_vp)), "ganq_debug_solve_plan")
+    return dict(regime=SOLVE_REGIMES[out[0]], k=out[1], helpers=out[2], grid=out[3])
+
+
+def debug_solve_role(active_tiles: int, cls: int, ticket: int, grid: int = 0, ncu: int = 0) -> dict:
+    """what ticket `ticket` of ticket class `cls` (blockIdx mod 8) makes a workgroup of that launch (ganq_debug_solve_role):
+    tile None = no role; stage 0 the tile, 1 / 2 a first / second helper serving `serves` tiles: tile, tile + 8, .."""
+    out = (ctypes.c_int * 3)()
+    _check(lib().ganq_debug_solve_role(int(active_tiles), int(grid), int(ncu), int(cls), int(ticket), ctypes.cast(out, _c_vp)),
+           "ganq_debug_solve_role")
+    return dict(tile=None if out[0] < 0 else out[0], stage=out[1], serves=out[2])
 
 
 LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*

@@ -83,6 +83,15 @@ enum Opt : int {
     OPT_KMEANS_SPAN,
     OPT_HESS_W4_WGS,
     OPT_KMEANS_QCAP,
+    OPT_SOLVE_SHARE,
+    OPT_SOLVE_SHARE_K,
+    OPT_SOLVE_SHARE2_XA,
+    OPT_SOLVE_SHARE2_XB,
+    OPT_SOLVE_SHARE3_XA,
+    OPT_SOLVE_SHARE3_XB,
+    OPT_SOLVE_SHARE4_XA,
+    OPT_SOLVE_SHARE4_XB,
+    OPT_SOLVE_CUS,
     OPT_COUNT
 };
 long long opt_get(int id);

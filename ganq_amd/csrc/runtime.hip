@@ -63,6 +63,15 @@ const OptDesc kOpts[OPT_COUNT] = {
     {"GANQ_KMEANS_SPAN", -1},      // windowed k-means: node spacing from which the levels are solved span by span (-1: default; 0: level by level as in rounds 1-3)
     {"GANQ_HESS_W4_WGS", 0},       // Hessian, staged groups (tests): cut the transposed path's launch for this many workgroups (0: one per CU)
     {"GANQ_KMEANS_QCAP", -1},      // resident k-means (tests): at most this many queued ranges per balanced level, below the plan's minimum of 128 -- the others are finished in place (-1: off)
+    {"GANQ_SOLVE_SHARE", 1},       // S-solve: 0 = never one helper workgroup for several tiles (solve_s.hip, "shared")
+    {"GANQ_SOLVE_SHARE_K", 0},     // ... tiles per shared helper: 0 = the smallest of 2 .. 4 that fits, 2 .. 4 (tests, sweeps) = that one or no helpers
+    {"GANQ_SOLVE_SHARE2_XA", 45},  // ... the tile's share of a chain of c with a helper for 2 tiles: max(XMIN, XA c / 64 - XB) (XMIN, CMIN: the duo's)
+    {"GANQ_SOLVE_SHARE2_XB", 0},
+    {"GANQ_SOLVE_SHARE3_XA", 53},  // ... for 3 tiles
+    {"GANQ_SOLVE_SHARE3_XB", 0},
+    {"GANQ_SOLVE_SHARE4_XA", 59},  // ... for 4 tiles
+    {"GANQ_SOLVE_SHARE4_XB", 0},
+    {"GANQ_SOLVE_CUS", 0},         // S-solve: > 0 = plan the helper regimes as if the chip had this many CUs (at most its own; tests)
 };
 
 std::atomic<long long> g_opt[OPT_COUNT];

@@ -566,10 +566,16 @@ __global__ __launch_bounds__(64) void l_pack_kernel(const float* __restrict__ L,
 // Launches with at most a third as many tiles as CUs ("trio") give a tile TWO helpers: the second takes the farthest half of
 // the helpers' share and hands its accumulators to the first, which continues and hands over to the tile -- a pipeline of three
 // CUs per chain; the tile's own share (trio_pol) is then small enough for its column steps to set the pace to the last panel.
-constexpr int DUO_MAX_TILES = 128;            // tiles with a helper (scratch is sized for them)
+// Launches with more tiles than half the CUs but idle CUs left over ("shared") give every k = 2 .. SHARE_MAX_K tiles of a ticket
+// class ONE helper workgroup: it takes a smaller far part of each of their chains (share_pol of k) and serves them in turn.  The
+// exchange per tile is the one above -- the tile does not know whom its helper also serves.  See the shared helper's loop below.
+constexpr int DUO_MAX_TILES = 128;            // tiles with a helper of their own
 constexpr int DUO_TRIO_TILES = 80;            // ... with two helpers each (a third of the chip)
+constexpr int SHARE_MAX_K = 4;                // tiles one shared helper serves at most
+constexpr int SHARE_MAX_TILES = 256;          // tiles with a FIRST helper, own or shared (the first helpers' scratch and the flags are sized
+                                              // for them; the second helpers' scratch for DUO_TRIO_TILES)
 constexpr int DUO_TW = 9;                     // flag words per tile: solved, ready[4] (helper -> tile), ready2[4] (second helper -> first)
-constexpr int DUO_CTRL_WORDS = 8 + DUO_MAX_TILES * DUO_TW;  // 8 ticket counters, then the tiles' flags
+constexpr int DUO_CTRL_WORDS = 8 + SHARE_MAX_TILES * DUO_TW;  // 8 ticket counters, then the tiles' flags (9 KB: one array for all)
 // s_memrealtime ticks (constant 100 MHz): 0.5 ms, about 60 column-panel steps (6-8 us each; 25 us for the last steps of n = 16384)
 // -- long enough for a helper that is resident but behind (it starts with a cold operand ring), short enough that a helper that is
 // NOT resident (another launch holds the CUs: side streams, a second process) costs a tile one wait of the order of the kernel's
@@ -586,6 +592,61 @@ __host__ __device__ __forceinline__ int duo_near(int c, int pol) {
     return x < c ? x : c;
 }
 
+// Which helpers a launch of A active tiles gets, and who a ticket makes a workgroup: ONE pair of functions for the host (grid,
+// ganq_debug_solve_plan) and the kernel, so that the two cannot disagree.
+enum : int { PLAN_NONE = 0, PLAN_SHARED = 1, PLAN_DUO = 2, PLAN_TRIO = 3 };
+enum : int { PLANF_HELPERS = 1, PLANF_TRIO = 2, PLANF_SHARE = 4 };
+struct SolvePlan {
+    int regime, k, helpers;  // k: tiles per first helper (1: duo / trio); helpers: helper workgroups with a role
+};
+struct SolveRole {
+    int tile;    // the tile, or the first tile a helper serves (ticket class + 8 i); SOLVE_SURPLUS: no role
+    int hstage;  // 0 the tile, 1 / 2 its first / second helper
+    int nserve;  // tiles a helper serves: tile, tile + 8, ..
+};
+constexpr int SOLVE_SURPLUS = 1 << 24;
+// tiles of ticket class cls (= blockIdx & 7 of the workgroups that draw there) among A active tiles: cls, cls + 8, ..
+__host__ __device__ __forceinline__ int class_tiles(int A, int cls) { return A > cls ? (A - cls + 7) >> 3 : 0; }
+// share_k: 0 = the smallest k that fits, 2 .. SHARE_MAX_K = that k or nothing
+__host__ __device__ inline SolvePlan solve_plan(int A, int grid, int ncu, int flags, int share_k) {
+    SolvePlan p = {PLAN_NONE, 0, 0};
+    if (!(flags & PLANF_HELPERS) || A <= 0) return p;
+    const int cap = grid < ncu ? grid : ncu, g8 = (A + 7) >> 3;
+    if ((flags & PLANF_TRIO) && A <= DUO_TRIO_TILES && 24 * g8 <= cap) return SolvePlan{PLAN_TRIO, 1, 2 * A};
+    if (A <= DUO_MAX_TILES && 16 * g8 <= cap) return SolvePlan{PLAN_DUO, 1, A};
+    // shared helpers are for launches that could not have had a helper per tile on this chip (more tiles than half the CUs)
+    if (!(flags & PLANF_SHARE) || 2 * A <= ncu || A > SHARE_MAX_TILES) return p;
+    const int k0 = share_k >= 2 && share_k <= SHARE_MAX_K ? share_k : 2, k1 = share_k >= 2 && share_k <= SHARE_MAX_K ? share_k : SHARE_MAX_K;
+    for (int k = k0; k <= k1; ++k) {
+        int total = 0;
+        bool fit = true;
+        for (int cls = 0; cls < 8; ++cls) {  // every ticket class holds its tiles and their helpers
+            const int tc = class_tiles(A, cls), need = tc + (tc + k - 1) / k;
+            fit = fit && need <= class_tiles(grid, cls);
+            total += need;
+        }
+        if (fit && total <= cap) return SolvePlan{PLAN_SHARED, k, total - A};
+    }
+    return p;
+}
+// Ticket tk of class cls.  Duo / trio: (tile, helper[, second helper]) in turn.  Shared: groups of (k tiles, then their helper); the
+// last group of a class holds the tiles left over, then its helper.  The tiles of a group draw before their helper: whatever
+// subset of the grid is resident, a helper that exists has all its tiles at least started.
+__host__ __device__ inline SolveRole solve_role(const SolvePlan& p, int A, int cls, int tk) {
+    if (p.regime == PLAN_DUO || p.regime == PLAN_TRIO) {
+        const int nh = p.regime == PLAN_TRIO ? 3 : 2, t = cls + 8 * (tk / nh);
+        return SolveRole{t < A ? t : SOLVE_SURPLUS, tk % nh, 1};
+    }
+    if (p.regime == PLAN_SHARED) {
+        const int k = p.k, tc = class_tiles(A, cls), full = tc / k, rem = tc - full * k;
+        const int g = tk / (k + 1), r = tk - g * (k + 1);
+        if (g < full) return r < k ? SolveRole{cls + 8 * (g * k + r), 0, 1} : SolveRole{cls + 8 * g * k, 1, k};
+        if (g == full && r < rem) return SolveRole{cls + 8 * (full * k + r), 0, 1};
+        if (g == full && r == rem && rem > 0) return SolveRole{cls + 8 * full * k, 1, rem};
+    }
+    return SolveRole{SOLVE_SURPLUS, 0, 0};
+}
+
 #ifndef GANQ_SOLVE_PRIME
 #define GANQ_SOLVE_PRIME 0  // measured: the chains start 0.2-0.5 us earlier and part 2 takes 0.3 us longer -- the chain waves are not
                             // the critical path of most steps; 4096 x 4096 1.05 vs 1.04 ms.  Off.  (The primed head assumes a chain
@@ -600,7 +661,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
                                                       const int* __restrict__ nactive, int opt_fast,
                                                       uint32_t* __restrict__ ctrl, float* __restrict__ Facc,
                                                       float* __restrict__ ErrH, uint32_t tag, int duo_pol, int ncu, int trio_pol,
-                                                      int64_t facc_stride, int64_t errh_stride) {
+                                                      int64_t facc_stride, int64_t errh_stride, int share_k, int share_pol2,
+                                                      int share_pol3, int share_pol4) {
     __shared__ float4 Ld[SPLIT ? 1 : 2][SPLIT ? 1 : SB][16];  // panel triangle of L, [jj][c16][k] <-> L[j0+jj][j0 + c16 + 16k]
     __shared__ __align__(16) float Ld4[SPLIT ? 2 * SB * SB : 4];  // split layout: [buf][jj][sub][k] <-> L[j0+jj][j0 + sub + 4k]
     __shared__ float Fs[SPLIT ? 3 : 1][SPLIT ? 16 : 1][16];    // split layout: sorted codebook, lo, hi of the 16 rows (set-up -> P wave)
@@ -627,15 +689,19 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
     int tile = blockIdx.x;
     bool duo = false, helper = false;
     int hstage = 0, nhelp = 1;  // this workgroup: 0 the tile, 1 / 2 its first / second helper; helpers per tile
+    int hserve = 0;             // shared helper: the tiles it serves (tile, tile + 8, ..); 0: a helper with one tile (duo / trio)
     int pol = duo_pol;          // the split policy in force
     if constexpr (!SPLIT) {
         if (duo_pol != 0 && GANQ_SOLVE_PRIME == 0) {
             const int A = (min(nact, m) + SR - 1) / SR;  // active tiles
-            duo = A <= DUO_MAX_TILES && 16 * ((A + 7) >> 3) <= min((int)gridDim.x, ncu);
-            if (trio_pol != 0 && A <= DUO_TRIO_TILES && 24 * ((A + 7) >> 3) <= min((int)gridDim.x, ncu)) {
-                duo = true;
+            const SolvePlan plan = solve_plan(A, (int)gridDim.x, ncu,
+                                              PLANF_HELPERS | (trio_pol != 0 ? PLANF_TRIO : 0) | (share_k >= 0 ? PLANF_SHARE : 0), share_k);
+            duo = plan.regime != PLAN_NONE;
+            if (plan.regime == PLAN_TRIO) {
                 nhelp = 2;
                 pol = trio_pol;
+            } else if (plan.regime == PLAN_SHARED) {
+                pol = plan.k == 2 ? share_pol2 : (plan.k == 3 ? share_pol3 : share_pol4);
             }
             if (duo) {  // roles by ticket (see above); a launch without helpers keeps tile = blockIdx and draws nothing
                 // one counter per residue class of blockIdx mod 8 (an XCD, when workgroups are dealt round-robin): 256 draws on one
@@ -650,10 +716,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
                     s_tk = t;
                 }
                 __syncthreads();
-                const int tk = (int)s_tk;
-                tile = cls + 8 * (tk / (nhelp + 1));
-                hstage = tk % (nhelp + 1);
+                const SolveRole role = solve_role(plan, A, cls, __builtin_amdgcn_readfirstlane((int)s_tk));
+                tile = role.tile;
+                hstage = role.hstage;
                 helper = hstage != 0;
+                hserve = plan.regime == PLAN_SHARED ? role.nserve : 0;
             }
         }
     }
@@ -778,6 +845,111 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
         }
         if (sink == 1.2345e-30f) ErrT[0] = sink;  // never true: keeps the loads
         return;
+    }
+    // ---- shared helper workgroup (serves hserve tiles: tile, tile + 8, ..): the feeder wave ---------------------------------------
+    // With a blocking wait the four chain waves of a helper reach the same conclusion by themselves; a poll that moves on to
+    // another tile does not -- two waves may read different values of a flag and disagree on what to do next.  So the choice of
+    // (tile, step) is made ONCE per round, by one wave, and handed to the chain waves through LDS.  Of the two ways to do that, the
+    // barrier-free one was chosen: wave 0 (a column-step wave, which has nothing to do in a helper) decides, copies the Err
+    // blocks the round needs from the tile's scratch -- into this workgroup's share of the LDS cache (the top `per` panels of each
+    // served tile) or its own copy in ErrH -- and only then publishes the round in a queue of HS_QN entries; each chain wave takes
+    // the rounds in order at its own pace and reports the last one taken.  After one barrier at the start (the queue's counters)
+    // no wave of a shared helper executes another, so none can reach one by a different path, and polling and copying run ahead of
+    // the chains instead of between them
+    // (with the choice made between the chains, behind a barrier: 139 tiles x 4096 0.67 ms at best, three and four tiles per helper
+    // no faster than no helper at all -- a round cost 5 us before its first matrix instruction).
+    // The feeder serves the tile that is furthest behind among those whose next panel is announced, and never waits on one tile's flag
+    // while another has work.  A tile that announces nothing for 16 x DUO_TIMEOUT is dropped (it gave up on this helper long
+    // before); the others are served on.  State per tile lives in LDS (the index staging area of the column steps is free in a
+    // helper): the step it is at, the lowest panel copied, when it was last seen with a panel announced (100 MHz ticks).
+    constexpr int HS_WR = 0, HS_RD = 4, HS_STEP = 8, HS_HAVE = 12, HS_SEEN = 16, HS_QUEUE = 32, HS_QN = 8;
+    constexpr uint32_t HS_EXIT = 0xffffffffu;
+    if constexpr (!SPLIT) {
+        if (helper && hserve > 0 && duo_pol >= 0 && wv == 0) {
+            volatile uint32_t* hs = &Qdm[0][0];
+            const int nbh = (n + SB - 1) / SB;
+            const int per = (nbh - pbase) / hserve, pb = nbh - per;
+            {
+                const uint32_t now = (uint32_t)__builtin_amdgcn_s_memrealtime();
+                if (lane < hserve) {
+                    hs[HS_STEP + lane] = 1u;
+                    hs[HS_HAVE + lane] = (uint32_t)nbh;
+                    hs[HS_SEEN + lane] = now;
+                }
+                if (lane < 8) hs[lane] = 0u;  // HS_WR, HS_RD
+            }
+            __syncthreads();  // the one barrier of a shared helper: the queue's counters start at zero for the chain waves
+            for (uint32_t rnd = 0;; ++rnd) {
+                if (rnd >= (uint32_t)HS_QN) {  // room in the queue: every chain wave has taken round rnd - HS_QN
+                    for (;;) {
+                        const uint32_t r0 = hs[HS_RD], r1 = hs[HS_RD + 1], r2 = hs[HS_RD + 2], r3 = hs[HS_RD + 3];
+                        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)min(min(r0, r1), min(r2, r3))) + (uint32_t)HS_QN > rnd) break;
+                        __builtin_amdgcn_s_sleep(2);
+                    }
+                }
+                int best = -1, best_s = 0;
+                for (;;) {  // (uniform over the wave: every lane reads the same words)
+                    const uint32_t now = (uint32_t)__builtin_amdgcn_s_memrealtime();
+                    bool pending = false;
+                    for (int i = 0; i < hserve; ++i) {
+                        int s = __builtin_amdgcn_readfirstlane((int)hs[HS_STEP + i]);
+                        while (s <= nbh - 1 && (s - 1) - duo_near(s - 1, pol) <= 0) ++s;  // steps whose chain the tile keeps whole
+                        if (lane == 0) hs[HS_STEP + i] = (uint32_t)s;
+                        if (s > nbh - 1) continue;  // served to the end, or dropped
+                        const int need = nbh - ((s - 1) - duo_near(s - 1, pol));
+                        bool avail = need >= __builtin_amdgcn_readfirstlane((int)hs[HS_HAVE + i]);  // nothing new to copy
+                        if (!avail) {  // panel p was solved in step nbh - p: has the tile announced that step?
+                            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(
+                                ctrl + 8 + DUO_TW * (tile + 8 * i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                            avail = (v ^ tag) < 1024u && (v & 1023u) >= (uint32_t)(nbh - need);
+                        }
+                        if (avail) {
+                            if (lane == 0) hs[HS_SEEN + i] = now;
+                            if (best < 0 || s < best_s) {
+                                best = i;
+                                best_s = s;
+                            }
+                        } else if (now - (uint32_t)__builtin_amdgcn_readfirstlane((int)hs[HS_SEEN + i]) > (uint32_t)(16 * DUO_TIMEOUT)) {
+                            if (lane == 0) hs[HS_STEP + i] = (uint32_t)nbh;  // dropped
+                        } else {
+                            pending = true;
+                        }
+                    }
+                    if (best >= 0 || !pending) break;  // a round to serve / every tile served or dropped
+                    __builtin_amdgcn_s_sleep(8);
+                }
+                uint32_t choice = HS_EXIT;
+                if (best >= 0) {
+                    choice = (uint32_t)best | ((uint32_t)best_s << 4);
+                    const int tl = tile + 8 * best;
+                    const int have = __builtin_amdgcn_readfirstlane((int)hs[HS_HAVE + best]);
+                    const int need = nbh - ((best_s - 1) - duo_near(best_s - 1, pol));
+                    if (need < have) {  // copy the new blocks, 4 KB each: 4 x 16 bytes per lane
+                        const __amdgpu_buffer_rsrc_t rsrcM =
+                            __builtin_amdgcn_make_buffer_rsrc(ErrT + (int64_t)tl * nbh * SBLK, 0, 0xffffffff, 0x00020000);  // the tile's blocks
+                        float* __restrict__ errh = ErrH + (int64_t)tl * nbh * SBLK;  // this workgroup's own copy (plain loads from here on)
+                        for (int pp = have - 1; pp >= need; --pp) {
+#pragma unroll
+                            for (int q4 = 0; q4 < SKR; ++q4) {
+                                const int e = (q4 * 64 + lane) * 4;
+                                const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrcM, e * 4, pp * SBLKB, 16));
+                                if (pp >= pb) *reinterpret_cast<f32x4v*>(ErrL + (best * per + pp - pb) * SBLK + e) = v;
+                                else *reinterpret_cast<f32x4v*>(errh + pp * SBLK + e) = v;
+                            }
+                        }
+                        if (lane == 0) hs[HS_HAVE + best] = (uint32_t)need;
+                    }
+                    if (lane == 0) hs[HS_STEP + best] = (uint32_t)(best_s + 1);
+                }
+                // the copies have arrived (LDS) / are acknowledged (memory) before the round is published
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                if (lane == 0) {
+                    hs[HS_QUEUE + (rnd & (uint32_t)(HS_QN - 1))] = choice;
+                    hs[HS_WR] = rnd + 1u;
+                }
+                if (choice == HS_EXIT) return;
+            }
+        }
     }
     if (helper && (!roleG || duo_pol < 0)) return;  // a helper workgroup is four chain waves (pol bit 31, tests: helpers that never answer)
     const int rsub = lane >> 4;
@@ -1143,6 +1315,10 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
     // zero records: every load through it is out of range and returns 0
     const __amdgpu_buffer_rsrc_t rsrcZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lr), 0, 0, 0x00020000);
     const int voff = lane * 16;  // this lane's 16 bytes inside each quarter of a packed block
+    // where a chain finds its A blocks: LDS holds the panels >= c_pbase from float c_eoff of ErrL on, the others come through
+    // c_rsrcE.  Constants of the launch for a tile and for a helper with one tile; a shared helper sets them per served tile.
+    int c_pbase = pbase, c_eoff = 0;
+    __amdgpu_buffer_rsrc_t c_rsrcE = rsrcE;
     // One chain segment: source panels phi, phi-1, .., plo (descending), A from LDS (panels >= pbase) or from
     // the global scratch.  One batch = one source panel = 16 MFMAs; operands are loaded two batches ahead into
     // three rotating register sets; every load is unconditional and the loop runs whole rounds of three
@@ -1162,12 +1338,12 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
             const int ps = phi - min(bi, nbat - 1);  // source panel of the batch
             const uint32_t sB = (uint32_t)lr_block(ct, ps, NT, nb) * (uint32_t)SBLKB;
             const __amdgpu_buffer_rsrc_t rsB = real ? rsrcL : rsrcZ;
-            const f32x4v* Al = reinterpret_cast<const f32x4v*>(ErrL + (ps - pbase) * SBLK + lane * 4);
+            const f32x4v* Al = reinterpret_cast<const f32x4v*>(ErrL + c_eoff + (ps - c_pbase) * SBLK + lane * 4);
 #pragma unroll
             for (int j = 0; j < SKR; ++j) {
                 bb[j] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsB, voff + 1024 * j, (int)sB, 0));
-                if (ALDS || (MIXED && ps >= pbase)) aa[j] = Al[j * 64];
-                else aa[j] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrcE, voff + 1024 * j, ps * SBLKB, 0));
+                if (ALDS || (MIXED && ps >= c_pbase)) aa[j] = Al[j * 64];
+                else aa[j] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(c_rsrcE, voff + 1024 * j, ps * SBLKB, 0));
             }
         };
         auto mm = [&](const f32x4v (&aa)[SKR], const f32x4v (&bb)[SKR]) {
@@ -1209,8 +1385,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
             const int ps = phi - min(bi, nbat - 1);
             const uint32_t sB = (uint32_t)lr_block(ct, ps, NT, nb) * (uint32_t)SBLKB;
             const __amdgpu_buffer_rsrc_t rsB = real ? rsrcL : rsrcZ;
-            const f32x4v* Al = reinterpret_cast<const f32x4v*>(ErrL + (ps - pbase) * SBLK + lane * 4);
-            const bool a_lds = ALDS || (MIXED && ps >= pbase);  // wave-uniform
+            const f32x4v* Al = reinterpret_cast<const f32x4v*>(ErrL + c_eoff + (ps - c_pbase) * SBLK + lane * 4);
+            const bool a_lds = ALDS || (MIXED && ps >= c_pbase);  // wave-uniform
 #pragma unroll
             for (int j = SKR - 1; j >= 0; --j) {
 #pragma unroll
@@ -1218,7 +1394,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
                 const int jl = SKR - 1 - j;
                 bn[jl] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsB, voff + 1024 * jl, (int)sB, 0));
                 if (a_lds) an[jl] = Al[jl * 64];
-                else an[jl] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrcE, voff + 1024 * jl, ps * SBLKB, 0));
+                else an[jl] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(c_rsrcE, voff + 1024 * jl, ps * SBLKB, 0));
             }
         };
         for (int bi = 0; bi < nbat; bi += RING) {  // whole rounds, no exits inside: a plain counted loop
@@ -1245,6 +1421,38 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
     // ---- helper workgroup: the far part of every panel's chain (see "duo" above) ---------------------------------------
     if (helper) {
         if constexpr (!SPLIT) {
+            if (hserve > 0) {
+                // ---- shared helper, the chain waves: one (tile, step) per round, as the feeder wave queued them (see "the feeder
+                // wave" above).  No workgroup barrier: a wave takes round rnd when the feeder has published it, and says so.
+                volatile uint32_t* hs = &Qdm[0][0];
+                const int per = (nb - pbase) / hserve;
+                c_pbase = nb - per;
+                __syncthreads();  // (the feeder has cleared the queue's counters)
+                for (uint32_t rnd = 0;; ++rnd) {
+                    while ((uint32_t)__builtin_amdgcn_readfirstlane((int)hs[HS_WR]) <= rnd) __builtin_amdgcn_s_sleep(1);
+                    const uint32_t choice = (uint32_t)__builtin_amdgcn_readfirstlane((int)hs[HS_QUEUE + (rnd & (HS_QN - 1))]);
+                    if (lane == 0) hs[HS_RD + gw] = rnd + 1u;  // (the entry has been read: LDS serves a wave in order)
+                    if (choice == HS_EXIT) return;
+                    const int ti = (int)(choice & 15u), s = (int)(choice >> 4), tl = tile + 8 * ti;
+                    const int h = (s - 1) - duo_near(s - 1, pol), need = nb - h;  // source panels nb-1 .. need are the helper's
+                    c_eoff = ti * per * SBLK;
+                    c_rsrcE = __builtin_amdgcn_make_buffer_rsrc(ErrH + (int64_t)tl * nb * SBLK, 0, 0xffffffff, 0x00020000);
+                    acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                    const int ct = SKR * (nb - 1 - s) + gw;  // this wave's 16-wide tile of panel bG = nb - 1 - s
+                    const int plds = max(need, c_pbase);
+                    chain(std::integral_constant<int, 1>{}, nb - 1, plds, ct, false);
+                    chain(std::integral_constant<int, 0>{}, min(nb - 1, plds - 1), need, ct, false);
+#if GANQ_MFMA_INPLACE
+                    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+#endif
+                    const __amdgpu_buffer_rsrc_t rsrcF =
+                        __builtin_amdgcn_make_buffer_rsrc(Facc + (int64_t)tl * (nb + 1) * SBLK, 0, 0xffffffff, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4raw, acc), rsrcF, voff + 1024 * gw, s * SBLKB, 16);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // acknowledged = visible to every CU
+                    if (lane == 0)
+                        __hip_atomic_store(ctrl + 8 + DUO_TW * tl + 1 + gw, tag | (uint32_t)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             const __amdgpu_buffer_rsrc_t rsrcM = __builtin_amdgcn_make_buffer_rsrc(errt, 0, 0xffffffff, 0x00020000);  // the tile's blocks
             // accumulators: out to the next stage (the tile, or the first helper), in from the second helper (first helper of a trio)
             const __amdgpu_buffer_rsrc_t rsrcF = __builtin_amdgcn_make_buffer_rsrc(
@@ -1472,6 +1680,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_s_kernel(const float* __r
 struct SolveLayout {
     int nb, NT;
     size_t errt_bytes, lr_bytes, facc_bytes, errh_bytes, ctrl_bytes, total;
+    int64_t facc_stride, errh_stride;  // floats from the first helpers' set to the second helpers' inside each pool
 };
 static SolveLayout solve_layout(int64_t m, int64_t n) {
     SolveLayout lo;
@@ -1481,9 +1690,16 @@ static SolveLayout solve_layout(int64_t m, int64_t n) {
     lo.errt_bytes = align_up((size_t)tiles * (size_t)lo.nb * SBLKB, 256);
     lo.lr_bytes = align_up((size_t)lo.nb * (size_t)lo.NT * SBLKB, 256);
     // helper workgroups (SB == 64 only): accumulators per (tile, step), the helpers' own copy of the Err blocks, flags
-    const size_t dt = SPLIT ? 0 : (size_t)std::min<int64_t>(tiles, DUO_MAX_TILES);
-    lo.facc_bytes = 2 * align_up(dt * (size_t)(lo.nb + 1) * SBLKB, 256);  // (x 2: one set per helper of a tile)
-    lo.errh_bytes = 2 * align_up(dt * (size_t)lo.nb * SBLKB, 256);
+    // One pool of per-tile slots for each.  The first helpers, own or shared, use slot `tile`: every tile that can have one, up to
+    // SHARE_MAX_TILES.  Second helpers exist only in launches of at most DUO_TRIO_TILES tiles, whose first helpers use the slots below
+    // that: theirs follow from there.  (256 slots at 4096 rows, what two sets for DUO_MAX_TILES took before the shared helpers.)
+    const size_t dt1 = SPLIT ? 0 : (size_t)std::min<int64_t>(tiles, SHARE_MAX_TILES);
+    const size_t dt2 = SPLIT ? 0 : (size_t)std::min<int64_t>(tiles, DUO_TRIO_TILES);
+    const size_t slots = std::max(dt1, 2 * dt2);
+    lo.facc_bytes = align_up(slots * (size_t)(lo.nb + 1) * SBLKB, 256);
+    lo.errh_bytes = align_up(slots * (size_t)lo.nb * SBLKB, 256);
+    lo.facc_stride = (int64_t)dt2 * (lo.nb + 1) * SBLK;
+    lo.errh_stride = (int64_t)dt2 * lo.nb * SBLK;
     lo.ctrl_bytes = align_up((size_t)DUO_CTRL_WORDS * sizeof(uint32_t), 256);
     lo.total = lo.errt_bytes + lo.lr_bytes + lo.facc_bytes + lo.errh_bytes + lo.ctrl_bytes;
     return lo;
@@ -1511,6 +1727,37 @@ int solve_s_pack_l(const float* L, int64_t ldl, int64_t m, int64_t n, void* work
                        mfma_k_ascending(), Lr, ctrl, DUO_CTRL_WORDS);
     GANQ_LAUNCH_CHECK();
     return 0;
+}
+
+// the CU count the helper regimes are planned for: `ncu` > 0 as given (ganq_debug_solve_plan without a GPU), else the current
+// device's -- or GANQ_SOLVE_CUS of them, if that is fewer (tests reach every regime with a few hundred rows; fewer helpers are
+// asked for than the chip could hold)
+static int solve_cus(int ncu) {
+    if (ncu <= 0) ncu = current_device_cus();
+    const int pretend = (int)opt_get(OPT_SOLVE_CUS);
+    return pretend > 0 && pretend < ncu ? pretend : ncu;
+}
+static int solve_plan_flags() {
+    return (opt_get(OPT_SOLVE_DUO) != 0 ? PLANF_HELPERS : 0) | (opt_get(OPT_SOLVE_TRIO) != 0 ? PLANF_TRIO : 0) |
+           (opt_get(OPT_SOLVE_SHARE) != 0 ? PLANF_SHARE : 0);
+}
+// workgroups of a launch that may have helpers: the tiles, or what the plan can need when all of them are active (with fewer
+// active tiles the kernel plans inside this grid; surplus workgroups leave at once)
+static int solve_grid(int tiles, int ncu) {
+    int grid = std::max(tiles, std::min(16 * ((tiles + 7) / 8), ncu / 16 * 16));
+    if (opt_get(OPT_SOLVE_TRIO) != 0 && ncu >= 24) grid = std::max(grid, std::min(24 * ((tiles + 7) / 8), ncu / 24 * 24));
+    if (opt_get(OPT_SOLVE_SHARE) != 0) {
+        const int fk = (int)opt_get(OPT_SOLVE_SHARE_K), tc = (tiles + 7) / 8;
+        for (int k = 2; k <= SHARE_MAX_K; ++k) {  // the smallest k that fits: every class as large as the fullest needs
+            if (fk >= 2 && fk <= SHARE_MAX_K && k != fk) continue;
+            const int cand = 8 * (tc + (tc + k - 1) / k);
+            if (solve_plan(tiles, cand, ncu, PLANF_HELPERS | PLANF_SHARE, k).regime == PLAN_SHARED) {
+                grid = std::max(grid, cand);
+                break;
+            }
+        }
+    }
+    return grid;
 }
 
 // the solve proper; the workspace already holds the packed L
@@ -1549,21 +1796,29 @@ int solve_s_launch(const float* W, const float* L, int64_t ldl, const float* T, 
     float* facc = reinterpret_cast<float*>(wsb + lo.errt_bytes + lo.lr_bytes);
     float* errh = reinterpret_cast<float*>(wsb + lo.errt_bytes + lo.lr_bytes + lo.facc_bytes);
     uint32_t* ctrl = reinterpret_cast<uint32_t*>(wsb + lo.errt_bytes + lo.lr_bytes + lo.facc_bytes + lo.errh_bytes);
-    const int ncu = current_device_cus();
-    int duo_pol = 0, trio_pol = 0, grid = tiles;
-    const int64_t facc_stride = (int64_t)(lo.facc_bytes / 2 / sizeof(float)), errh_stride = (int64_t)(lo.errh_bytes / 2 / sizeof(float));
+    const int ncu = solve_cus(0);
+    int duo_pol = 0, trio_pol = 0, grid = tiles, share_k = -1, share_pol[3] = {0, 0, 0};
+    const int64_t facc_stride = lo.facc_stride, errh_stride = lo.errh_stride;
     if (!SPLIT && allow_helpers && opt_get(OPT_SOLVE_DUO) != 0 && ncu >= 16 && lo.nb <= 1000) {
         const int xa = (int)opt_get(OPT_SOLVE_DUO_XA), xb = (int)opt_get(OPT_SOLVE_DUO_XB), xmin = (int)opt_get(OPT_SOLVE_DUO_XMIN),
                   cmin = (int)opt_get(OPT_SOLVE_DUO_CMIN);
         const int pol = (xa & 255) | ((xb & 255) << 8) | ((std::max(xmin, 1) & 255) << 16) | ((std::max(cmin, 1) & 127) << 24);
         if (lo.nb - 2 >= std::max(cmin, 1)) {  // some chain is long enough to be shared
             duo_pol = opt_get(OPT_SOLVE_DUO) == 2 ? (int)((unsigned)pol | 0x80000000u) : pol;  // 2 (tests): mute helpers, see the kernel
-            grid = std::max(tiles, std::min(16 * ((tiles + 7) / 8), ncu / 16 * 16));
+            grid = solve_grid(tiles, ncu);
             // two helpers per tile where a third of the chip holds the tiles: its own split policy (the tile keeps less)
             if (opt_get(OPT_SOLVE_TRIO) != 0 && ncu >= 24) {
                 const int xa3 = (int)opt_get(OPT_SOLVE_TRIO_XA), xb3 = (int)opt_get(OPT_SOLVE_TRIO_XB);
                 trio_pol = (xa3 & 255) | ((xb3 & 255) << 8) | ((std::max(xmin, 1) & 255) << 16) | ((std::max(cmin, 1) & 127) << 24);
-                grid = std::max(grid, std::min(24 * ((tiles + 7) / 8), ncu / 24 * 24));
+            }
+            // one helper for every k tiles where idle CUs are left but not one per tile: a policy per k (the tile keeps more)
+            if (opt_get(OPT_SOLVE_SHARE) != 0) {
+                share_k = (int)opt_get(OPT_SOLVE_SHARE_K);
+                share_k = share_k >= 2 && share_k <= SHARE_MAX_K ? share_k : 0;
+                const int xas[3] = {(int)opt_get(OPT_SOLVE_SHARE2_XA), (int)opt_get(OPT_SOLVE_SHARE3_XA), (int)opt_get(OPT_SOLVE_SHARE4_XA)};
+                const int xbs[3] = {(int)opt_get(OPT_SOLVE_SHARE2_XB), (int)opt_get(OPT_SOLVE_SHARE3_XB), (int)opt_get(OPT_SOLVE_SHARE4_XB)};
+                for (int i = 0; i < 3; ++i)
+                    share_pol[i] = (xas[i] & 255) | ((xbs[i] & 255) << 8) | ((std::max(xmin, 1) & 255) << 16) | ((std::max(cmin, 1) & 127) << 24);
             }
         }
     }
@@ -1576,10 +1831,12 @@ int solve_s_launch(const float* W, const float* L, int64_t ldl, const float* T, 
     if (SOLVE_PF && tiles <= 256 && n > 4096) fast |= 2;
     if (mfma_k_ascending()) {
         hipLaunchKernelGGL(solve_s_kernel<true>, dim3(grid), dim3(SOLVE_THREADS), smem, stream, W, L, ldl, Lr, lo.NT, T, (int)m, (int)n,
-                           V, Q_out, Err_out, errt, pbase, rowlist, nactive, fast, ctrl, facc, errh, tag, duo_pol, ncu, trio_pol, facc_stride, errh_stride);
+                           V, Q_out, Err_out, errt, pbase, rowlist, nactive, fast, ctrl, facc, errh, tag, duo_pol, ncu, trio_pol, facc_stride, errh_stride,
+                           share_k, share_pol[0], share_pol[1], share_pol[2]);
     } else {
         hipLaunchKernelGGL(solve_s_kernel<false>, dim3(grid), dim3(SOLVE_THREADS), smem, stream, W, L, ldl, Lr, lo.NT, T, (int)m, (int)n,
-                           V, Q_out, Err_out, errt, pbase, rowlist, nactive, fast, ctrl, facc, errh, tag, duo_pol, ncu, trio_pol, facc_stride, errh_stride);
+                           V, Q_out, Err_out, errt, pbase, rowlist, nactive, fast, ctrl, facc, errh, tag, duo_pol, ncu, trio_pol, facc_stride, errh_stride,
+                           share_k, share_pol[0], share_pol[1], share_pol[2]);
     }
     GANQ_LAUNCH_CHECK();
     return 0;
@@ -1604,6 +1861,32 @@ extern "C" int ganq_debug_solve_counters(unsigned long long* out4) {
     return 0;
 }
 #endif
+
+extern "C" int ganq_debug_solve_plan(int active_tiles, int grid, int ncu, int* out) {
+    if (!out) return fail(-3, "ganq_debug_solve_plan: null pointer");
+    if (active_tiles <= 0 || ncu < 0) return fail(-1, "ganq_debug_solve_plan: bad arguments");
+    const int cus = solve_cus(ncu);  // (asks the device only for ncu == 0)
+    if (grid <= 0) grid = solve_grid(active_tiles, cus);
+    const SolvePlan p = SPLIT || cus < 16 ? SolvePlan{PLAN_NONE, 0, 0}
+                                          : solve_plan(active_tiles, grid, cus, solve_plan_flags(), (int)opt_get(OPT_SOLVE_SHARE_K));
+    out[0] = p.regime;
+    out[1] = p.k;
+    out[2] = p.helpers;
+    out[3] = grid;
+    return 0;
+}
+
+extern "C" int ganq_debug_solve_role(int active_tiles, int grid, int ncu, int cls, int ticket, int* out) {
+    int pl[4];
+    if (!out || cls < 0 || cls > 7 || ticket < 0) return fail(-1, "ganq_debug_solve_role: bad arguments");
+    const int rc = ganq_debug_solve_plan(active_tiles, grid, ncu, pl);
+    if (rc) return rc;
+    const SolveRole r = solve_role(SolvePlan{pl[0], pl[1], pl[2]}, active_tiles, cls, ticket);
+    out[0] = pl[0] == PLAN_NONE || r.tile == SOLVE_SURPLUS ? -1 : r.tile;
+    out[1] = r.hstage;
+    out[2] = r.nserve;
+    return 0;
+}
 
 extern "C" size_t ganq_solve_s_workspace_bytes(int64_t m, int64_t n, int V) {
     (void)V;

@@ -144,11 +144,25 @@ int ganq_debug_kmeans_plan(int64_t m, int64_t n, int V, int* out);
  * W [m,n], L [n,n] lower-triangular with leading dimension ldl, T [m,V].
  * Q_out [m,n] uint8.  Err_out [m,n] fp32 (W - T[Q]; the Metal kernel's `Werr`) or NULL.
  * workspace: ganq_solve_s_workspace_bytes() -- the per-tile Err scratch and the packed copy of L, plus the
- * hand-over buffers of the helper workgroups that launches with at most half as many 16-row tiles as
- * the chip has CUs use (csrc/solve_s.hip, "duo"); contents need no initialisation.              */
+ * hand-over buffers of the helper workgroups that launches with fewer 16-row tiles than the chip has
+ * CUs use (csrc/solve_s.hip, "duo" / "shared"); contents need no initialisation.                */
 size_t ganq_solve_s_workspace_bytes(int64_t m, int64_t n, int V);
 int ganq_solve_s(const float* W, const float* L, int64_t ldl, const float* T, int64_t m, int64_t n, int V,
                  uint8_t* Q_out, float* Err_out, void* workspace, size_t workspace_bytes, void* stream);
+/* which helper workgroups a launch of ganq_solve_s with `active_tiles` 16-row tiles still to solve gets under the current
+ * developer options, from the plan function the kernel itself evaluates (host only; the device is asked for its CU count only
+ * when ncu == 0, and GANQ_SOLVE_CUS caps either).  grid: workgroups of the launch, <= 0 = what the host launches for a layer
+ * of active_tiles tiles.  Chains are assumed long enough for helpers (more than GANQ_SOLVE_DUO_CMIN + 1 panels of 64 columns).
+ * out[4] = { regime, k: tiles per first helper (1 for DUO / TRIO, 0 for NONE), helper workgroups, grid }. */
+#define GANQ_SOLVE_PLAN_NONE 0   /* no helpers: no tickets are drawn */
+#define GANQ_SOLVE_PLAN_SHARED 1 /* one helper for every k = 2 .. 4 tiles of a ticket class */
+#define GANQ_SOLVE_PLAN_DUO 2    /* a helper per tile (at most half as many tiles as CUs) */
+#define GANQ_SOLVE_PLAN_TRIO 3   /* two helpers per tile (at most a third) */
+int ganq_debug_solve_plan(int active_tiles, int grid, int ncu, int* out);
+/* ... and what ticket `ticket` of class cls (blockIdx mod 8) makes a workgroup of that launch:
+ * out[3] = { tile (a helper: the first tile it serves; -1: no role, the workgroup leaves), 0 tile / 1 first / 2 second helper,
+ *            tiles a helper serves: tile, tile + 8, .. }. */
+int ganq_debug_solve_role(int active_tiles, int grid, int ncu, int cls, int ticket, int* out);
 
 /* ---- dense fp32 product C[m,n] = A[m,k] @ B[k,n] on the fp32 matrix cores (W@H, ganq.py:590) */
 int ganq_matmul_f32(const float* A, const float* B, int64_t m, int64_t k, int64_t n, float* C, void* stream);

@@ -54,6 +54,7 @@ SIGNATURES = {
     "ganq_debug_kmeans_plan": (ctypes.c_int, [_c_i64, _c_i64, ctypes.c_int, _c_vp]),
     "ganq_solve_s_workspace_bytes": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "ganq_debug_solve_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
+    "ganq_debug_accum_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _c_vp]),
     "ganq_debug_solve_role": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "ganq_solve_s": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp,
                                     _c_sz, _c_vp]),
@@ -722,6 +723,17 @@ def debug_solve_role(active_tiles: int, cls: int, ticket: int, grid: int = 0, nc
     _check(lib().ganq_debug_solve_role(int(active_tiles), int(grid), int(ncu), int(cls), int(ticket), ctypes.cast(out, _c_vp)),
            "ganq_debug_solve_role")
     return dict(tile=None if out[0] < 0 else out[0], stage=out[1], serves=out[2])
+
+
+ACCUM_KERNELS = ("onehot_accum", "onehot_accum_w4")
+
+
+def accum_plan(m: int, n: int) -> dict:
+    """which kernel the T-update's full bucket sum of an [m, n] layer runs under the current developer options
+    (ganq_debug_accum_plan: the function the launch evaluates; no GPU needed).  supported: the four-wave kernel serves the shape."""
+    out = (ctypes.c_int * 2)()
+    _check(lib().ganq_debug_accum_plan(int(m), int(n), ctypes.cast(out, _c_vp)), "ganq_debug_accum_plan")
+    return dict(kernel=ACCUM_KERNELS[out[0]], supported=bool(out[1]))
 
 
 LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*

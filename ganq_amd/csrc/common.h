@@ -92,6 +92,7 @@ enum Opt : int {
     OPT_SOLVE_SHARE4_XA,
     OPT_SOLVE_SHARE4_XB,
     OPT_SOLVE_CUS,
+    OPT_ACCUM_W4,
     OPT_COUNT
 };
 long long opt_get(int id);

@@ -72,6 +72,7 @@ const OptDesc kOpts[OPT_COUNT] = {
     {"GANQ_SOLVE_SHARE4_XA", 59},  // ... for 4 tiles
     {"GANQ_SOLVE_SHARE4_XB", 0},
     {"GANQ_SOLVE_CUS", 0},         // S-solve: > 0 = plan the helper regimes as if the chip had this many CUs (at most its own; tests)
+    {"GANQ_ACCUM_W4", -1},         // T-update, full bucket sum: 1 = the four-wave kernel wherever it is supported (in_features a multiple of 256), 0 = never (-1: by shape, accum_plan in update_t.hip)
 };
 
 std::atomic<long long> g_opt[OPT_COUNT];

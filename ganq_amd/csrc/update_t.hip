@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "common.h"
+#include "mfma_h16.h"
 #include "update_t.h"
 #include "wh_gemm.h"
 
@@ -435,6 +436,331 @@ __global__ __launch_bounds__(TW * 64) void onehot_accum_kernel(const int8_t* __r
     if (changed && *changed <= thr) return;
     if ((int)blockIdx.x < nblk_hi) onehot_accum_body<4, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
     else onehot_accum_body<2, 4>(planes_all, bits, Q, m, n, nq, ng, Mpart_lo, nullptr, prep, (int)blockIdx.x - nblk_hi);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The full accumulation, second implementation: FOUR waves, one per SIMD, 8 rows per wave (GANQ_ACCUM_W4, accum_plan below).
+// The same integers as onehot_accum_kernel from the same planes, masks and partial-sum layout; what differs is the schedule:
+//   * a wave owns 4 row pairs x NPL planes = 16 accumulator tiles of 32 x 32 (256 registers with four planes), pinned to the
+//     accumulation registers by asm "+a" operands (mfma_h16.h says why); a B fragment read from LDS feeds 4 matrix instructions
+//     instead of 2, and the vector registers hold two real sets of B fragments: the next 32-column half is read while this
+//     half's 16 matrix instructions run;
+//   * the digit tiles go global -> LDS by LDS-DMA in SLICES of 128 columns u (NPL planes x 32 v x 128 B) through a ring of four
+//     stages that runs across the chunks of a workgroup: slice f + 3 of the workgroup's flat (chunk, slice) sequence is requested
+//     during slice f, so a chunk opens without a store or a barrier of its own.  One counted s_waitcnt vmcnt and one barrier
+//     per slice: behind them slice f + 1 has landed for every wave and the stage of slice f - 1 is free;
+//   * an LDS-DMA image is lane-linear and cannot be padded: the 16-byte slot of a 128-byte row is XORed with (v >> 1) & 7 on the
+//     fetch side (the global source slot) and on the read side, so the 16 lanes of a quarter wave read 16 different bank groups;
+//   * the diagonal: only a chunk's first slice holds bytes with u <= v.  With v0 a multiple of 32 its 32-column halves left of
+//     v0 and the 32 x 32 block on the diagonal are masked IN THE FRAGMENT REGISTERS (a per-lane constant of four dwords) --
+//     cheaper than zeroing the landed block in LDS, which would put a wait for the slice and an LDS write in front of the
+//     barrier that releases it.  `planes` is only read.
+// n must be a multiple of 256 (whole slices, every chunk has a first slice, nq == n).
+constexpr int W4_SU = 128;   // u per slice
+constexpr int W4_NST = 4;    // LDS stages
+constexpr int W4_RING = W4_NST * 4 * 32 * W4_SU;  // bytes of the ring with four planes (the extension's two planes use half of every stage)
+constexpr size_t W4_LDS = (size_t)W4_RING + 4 * 8 * 256 * sizeof(long long);
+
+struct W4It {  // (chunk, slice) in the flat slice sequence of a workgroup
+    int c, s;
+};
+__device__ __forceinline__ void w4_next(W4It& it, int ns, int nchunk) {
+    if (it.s + 1 < ns) ++it.s;
+    else if (it.c + NP < nchunk) {
+        it.c += NP;
+        it.s = it.c >> 2;  // the slice that holds u = v0 + 1
+    }
+    // past the end: stays on the last slice -- fetched again into a stage nobody reads, so that the counted waits stay uniform
+}
+// FIRST: the first matrix instruction behind vector instructions that wrote its operands (hipcc's hazard recogniser does not see a
+// matrix instruction inside an asm statement)
+template <bool FIRST>
+__device__ __forceinline__ void w4_mfma(v16i& acc, const v4i& a, const v4i& b) {
+    if constexpr (FIRST) asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void w4_mfma_zero(v16i& acc, const v4i& z) {  // acc = 0, born in an accumulation register
+    asm volatile("s_nop 4\n\tv_mfma_i32_32x32x32_i8 %0, %1, %1, 0" : "=a"(acc) : "v"(z));
+}
+// Loads and LDS atomics the COMPILER DOES NOT COUNT: with LDS-DMA in flight hipcc waits for vmcnt(0) in front of every use of a
+// loaded register and of every LDS atomic (it cannot tell what the DMA may still write), which would drain the ring once per slice.
+// The waits are written out instead (accum_w4_body: wait_masks / wait_codes name the registers, so no use moves in front of them;
+// request and wait stand in the same pass of the slice loop, so the compiler has no copy of a register in flight to make).
+__device__ __forceinline__ uint32_t w4_load_u32(const void* sbase, uint32_t voff) {
+    uint32_t r;
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
+    return r;
+}
+__device__ __forceinline__ uint32_t w4_load_u8(const void* sbase, uint32_t voff) {
+    uint32_t r;
+    asm volatile("global_load_ubyte %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
+    return r;
+}
+__device__ __forceinline__ void w4_lds_add_u64(uint32_t addr, unsigned long long v) {
+    asm volatile("ds_add_u64 %0, %1" : : "v"(addr), "v"(v) : "memory");
+}
+
+template <int NPL, int P0>
+__device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_all, const unsigned long long* __restrict__ bits,
+                                              const uint8_t* __restrict__ Q, int m, int n, int nq, int ng,
+                                              long long* __restrict__ Mpart, long long* __restrict__ stamps,
+                                              const TPrep* __restrict__ prep, const int bid) {
+    if (P0 != 0 && prep->ext == 0) return;
+    constexpr int ST = NPL * 32 * W4_SU;  // bytes per stage
+    constexpr int NI = ST / 1024 / 4;     // LDS-DMA instructions (64 lanes x 16 B) per wave and slice
+    constexpr int HSTEP = 4 / NI;         // ... one in front of every HSTEP-th half
+    extern __shared__ __align__(1024) char w4_smem[];
+    char* const ring = w4_smem;
+    long long(*Mrow)[8][256] = reinterpret_cast<long long(*)[8][256]>(w4_smem + W4_RING);  // [wave][row][a * 16 + b]
+    const int8_t* planes = planes_all + (int64_t)P0 * n * nq;
+    long long st_pro = 0, st_loop = 0, st_flush = 0;
+    long long st_t0 = __builtin_amdgcn_s_memtime();
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the LDS-DMA destinations are scalar arithmetic)
+    // v_mfma_i32_32x32x32_i8 as in onehot_accum_body: A rows = (row of the pair, code), B columns = the chunk's 32 v
+    const int i32 = lane & 31, kb = lane >> 5;
+    const int r2 = i32 >> 4, a16 = i32 & 15;
+    const int nrg = (m + 31) / 32;
+    const int rg = bid % nrg, part = bid / nrg;
+    const int row0 = rg * 32 + wv * 8;
+    const int ns = n / W4_SU, nchunk = n / 32;
+    int mrow[4];  // the row whose masks this lane expands, per row pair
+#pragma unroll
+    for (int p = 0; p < 4; ++p) mrow[p] = min(row0 + 2 * p + r2, m - 1);
+    for (int i = lane; i < 8 * 256; i += 64) Mrow[wv][i >> 8][i & 255] = 0;
+
+    // LDS-DMA: one instruction = 8 rows (plane, v) x 128 B; wave wv sends instructions NI wv .. NI wv + NI - 1 of a slice.  Lane l
+    // writes slot l & 7 of row l >> 3 and fetches the slot that belongs there under the XOR
+    uint32_t doff[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int rl = (wv * NI + i) * 8 + (lane >> 3);  // row of the stage: plane rl >> 5, v rl & 31
+        const int g = (lane & 7) ^ ((rl >> 1) & 7);
+        doff[i] = (uint32_t)(((size_t)(rl >> 5) * n + (rl & 31)) * nq + 16 * g);
+    }
+    auto dma = [&](const W4It& it, int stage, int i) {
+        const int8_t* src = planes + (size_t)(32 * it.c) * nq + W4_SU * it.s;
+        char* dst = ring + stage * ST + (wv * NI + i) * 1024;
+        __builtin_amdgcn_global_load_lds((hg_gptr)(src + doff[i]), (hg_lptr)dst, 16, 0, 0);
+    };
+    uint32_t wc[2][4], wn[2][4], bq[8];  // masks of this slice / requested for the next one; the chunk's codes
+    // everything but the NI LDS-DMA instructions issued last has landed: the slice before theirs, and the masks / codes requested
+    // in front of them
+    auto wait_masks = [&]() {
+        if constexpr (NI == 4)
+            asm volatile("s_waitcnt vmcnt(4)" : "+v"(wn[0][0]), "+v"(wn[0][1]), "+v"(wn[0][2]), "+v"(wn[0][3]), "+v"(wn[1][0]), "+v"(wn[1][1]), "+v"(wn[1][2]), "+v"(wn[1][3]) : : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(2)" : "+v"(wn[0][0]), "+v"(wn[0][1]), "+v"(wn[0][2]), "+v"(wn[0][3]), "+v"(wn[1][0]), "+v"(wn[1][1]), "+v"(wn[1][2]), "+v"(wn[1][3]) : : "memory");
+    };
+    auto take_masks = [&]() {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) wc[ks][p] = wn[ks][p];
+    };
+    auto wait_codes = [&]() {
+        if constexpr (NI == 4)
+            asm volatile("s_waitcnt vmcnt(4)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(2)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+    };
+    // fragment reads: lane l holds column v = l & 31, bytes 16 (l >> 5) .. + 15 of a 32-column half; half h: address ^ (h << 5)
+    const uint32_t rd0 = (uint32_t)(uintptr_t)ring + (uint32_t)(i32 * 128 + ((kb ^ ((i32 >> 1) & 7)) << 4));
+    auto read_b = [&](int stage, int h, v4i (&bf)[NPL]) {
+        typedef const v4i __attribute__((address_space(3))) * lp;
+        const uint32_t a = (rd0 + (uint32_t)(stage * ST)) ^ (uint32_t)(h << 5);
+#pragma unroll
+        for (int d = 0; d < NPL; ++d) bf[d] = *reinterpret_cast<lp>(a + d * 4096);
+    };
+    // the block on the diagonal: byte 16 kb + 4 j + b of column i32 stays when it lies right of the diagonal
+    v4i dmask;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int cnt = min(4, max(0, i32 - (16 * kb + 4 * j) + 1));  // leading bytes to clear
+        dmask[j] = cnt >= 4 ? 0 : (int)(0xffffffffu << (8 * cnt));
+    }
+    // code masks in the layout of code_masks_kernel: one dword per 64-column step and row pair, requested one slice ahead
+    // (scalar base of the step + 32-bit lane offset: m n < 2^31, accum_w4_supported)
+    uint32_t moff[4], qoff[8];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) moff[p] = (uint32_t)((((size_t)mrow[p] * ng * 16 + a16) * 2 + kb) * 4);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) qoff[r] = (uint32_t)((size_t)min(row0 + r, m - 1) * n + i32);
+    auto load_masks = [&](const W4It& it) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const unsigned long long* base = bits + (size_t)(2 * it.s + ks) * 16;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) wn[ks][p] = w4_load_u32(base, moff[p]);
+        }
+    };
+
+    v16i acc[4][NPL];
+    const v4i zero4 = v4i{0, 0, 0, 0};
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int d = 0; d < NPL; ++d) w4_mfma_zero(acc[p][d], zero4);
+    v4i bf[2][NPL];
+
+    // prologue: slices 0 .. 2 in flight, the masks of slice 0; then slice 0 has landed for everybody
+    W4It msk{part, part >> 2}, iss = msk;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) dma(iss, b, i);
+        w4_next(iss, ns, nchunk);
+    }
+    load_masks(msk);
+    w4_next(msk, ns, nchunk);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) dma(iss, 2, i);
+    w4_next(iss, ns, nchunk);
+    wait_masks();
+    take_masks();
+    __builtin_amdgcn_s_barrier();
+    read_b(0, 0, bf[0]);
+    { const long long tt = __builtin_amdgcn_s_memtime(); st_pro += tt - st_t0; st_t0 = tt; }
+
+    int f = 0;  // flat slice count: slice f lives in stage f & 3
+    for (int c = part; c < nchunk; c += NP) {
+        const int v0 = 32 * c;
+        const int hd = c & 3;  // the half of the chunk's first slice that holds the diagonal
+        auto slice = [&](auto diag_tag) {
+            constexpr bool DIAG = decltype(diag_tag)::value;
+            const int stage = f & 3;
+            // slice f + 1 has landed (this wave's share: the wait that closed slice f - 1); behind the barrier: everybody's, and
+            // every wave is through slice f - 1: its stage takes slice f + 3
+            __builtin_amdgcn_s_barrier();
+            if (DIAG) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) bq[r] = w4_load_u8(Q + v0, qoff[r]);
+            }
+            load_masks(msk);
+            w4_next(msk, ns, nchunk);
+            // A one-hot fragment = 4 dwords, each 3 vector instructions (16 mask bits -> 16 bytes).  The wave is alone on its SIMD:
+            // whatever it issues between two matrix instructions hides behind the first one, whatever it issues in a row does
+            // not.  So the fragment of the NEXT group of NPL matrix instructions is expanded piece by piece between those of this
+            // one (measured: expanded in one piece in front of its group, the tile loop was no faster than the first kernel's),
+            // and the LDS reads and the LDS-DMA of a half stand behind its first matrix instruction.
+            auto piece = [&](int h, int p, int d) {
+                return (int)((((wc[h >> 1][p] >> (16 * (h & 1) + 4 * d)) & 0xfu) * 0x00204081u) & 0x01010101u);
+            };
+            v4i af[2];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) af[0][d] = piece(0, 0, d);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                auto feed = [&]() {  // this half's share of the slice's LDS-DMA; the B fragments of the next half / slice
+                    if (h % HSTEP == 0) dma(iss, (f + 3) & 3, h / HSTEP);
+                    if (h < 3) read_b(stage, h + 1, bf[(h + 1) & 1]);
+                    else read_b((f + 1) & 3, 0, bf[0]);
+                };
+                if (DIAG) {
+                    // a chunk's first slice: the halves left of v0 count nothing, the one at v0 what lies right of the diagonal.
+                    // Masked, not skipped (at most three halves of matrix work per chunk): with branches around the asm
+                    // statements hipcc moves accumulator tiles between the register files again (112 spilled registers)
+                    const int keep = h > hd ? -1 : 0, on = h == hd ? -1 : 0;
+#pragma unroll
+                    for (int d = 0; d < NPL; ++d)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) bf[h & 1][d][j] &= keep | (on & dmask[j]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("s_nop 4" ::: "memory");  // (the masked fragments were written just now)
+                }
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int g = 4 * h + p;           // parity of the fragment register set
+                    const bool more = 4 * h + p < 15;  // the group behind this one is in this slice
+                    const int nh = p < 3 ? h : h + 1, np = (p + 1) & 3;
+#pragma unroll
+                    for (int d = 0; d < NPL; ++d) {
+                        if (d == 0) w4_mfma<true>(acc[p][0], af[g & 1], bf[h & 1][0]);
+                        else w4_mfma<false>(acc[p][d], af[g & 1], bf[h & 1][d]);
+                        if (p == 0 && d == 0) feed();
+                        if (more && d < NPL - 1) {  // pieces of the next fragment; none behind the group's last instruction
+                            constexpr int PER = 4 / (NPL - 1) + (4 % (NPL - 1) != 0);
+#pragma unroll
+                            for (int k = d * PER; k < min(4, (d + 1) * PER); ++k) af[(g + 1) & 1][k] = piece(nh, np, k);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+            w4_next(iss, ns, nchunk);
+            ++f;
+            // all but the LDS-DMA of this pass has landed: slice f + 1, the masks of slice f (and the chunk's codes)
+            if (DIAG) wait_codes();
+            wait_masks();
+            take_masks();
+        };
+        slice(std::true_type{});
+        for (int s = (c >> 2) + 1; s < ns; ++s) slice(std::false_type{});
+        { const long long tt = __builtin_amdgcn_s_memtime(); st_loop += tt - st_t0; st_t0 = tt; }
+        // bucket the chunk's columns by their code, as onehot_accum_body does.  The accumulation registers are read behind matrix
+        // instructions in asm statements: the wait is written out, tied to the registers so that no read moves in front of it
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            if constexpr (NPL == 4)
+                asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]), "+a"(acc[p][2]), "+a"(acc[p][3]));
+            else asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]));
+        }
+        const uint32_t mrow0 = (uint32_t)(uintptr_t)&Mrow[wv][0][0];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int i = (reg & 3) + 8 * (reg >> 2) + 4 * kb;  // (row of the pair, code)
+                const int h = i >> 4, a = i & 15;
+                // |digit sum| <= 128 n <= 2^22 (n <= 32768): two digits recombine inside 32 bits.  No branch around the atomic (64 of
+                // them per chunk cost more than the additions they saved): a code outside 0 .. 15 adds zero to bucket b & 15
+                long long val = (long long)(acc[p][0][reg] + (acc[p][1][reg] << 8));
+                if constexpr (NPL == 4) val += (long long)(acc[p][2][reg] + (acc[p][3][reg] << 8)) << 16;
+                const uint32_t b = h ? bq[2 * p + 1] : bq[2 * p];
+                if (b >= 16u) val = 0;
+                w4_lds_add_u64(mrow0 + (uint32_t)((((2 * p + h) * 16 + a) * 16 + (b & 15u)) * 8), (unsigned long long)val);
+            }
+#pragma unroll
+            for (int d = 0; d < NPL; ++d) w4_mfma_zero(acc[p][d], zero4);
+        }
+        { const long long tt = __builtin_amdgcn_s_memtime(); st_flush += tt - st_t0; st_t0 = tt; }
+    }
+    // no LDS-DMA may be in flight when the workgroup's LDS is handed on; the bucket sums are complete
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (stamps && bid == 0 && tid == 0) { stamps[0] = st_pro; stamps[1] = st_loop; stamps[2] = st_flush; }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (row0 + r < m) {
+            long long* out = Mpart + ((int64_t)part * m + row0 + r) * 256;
+            for (int i = lane; i < 256; i += 64) out[i] = Mrow[wv][r][i];
+        }
+}
+
+// one launch for both words, as onehot_accum_kernel
+__global__ __launch_bounds__(256, 1) void onehot_accum_w4_kernel(const int8_t* __restrict__ planes_all,
+                                                                const unsigned long long* __restrict__ bits,
+                                                                const uint8_t* __restrict__ Q, int m, int n, int nq, int ng,
+                                                                long long* __restrict__ Mpart_hi, long long* __restrict__ Mpart_lo,
+                                                                long long* __restrict__ stamps, const long long* __restrict__ changed,
+                                                                long long thr, const TPrep* __restrict__ prep, int nblk_hi) {
+    if (changed && *changed <= thr) return;
+    if ((int)blockIdx.x < nblk_hi) accum_w4_body<4, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
+    else accum_w4_body<2, 4>(planes_all, bits, Q, m, n, nq, ng, Mpart_lo, nullptr, prep, (int)blockIdx.x - nblk_hi);
+}
+
+// which kernel sums the buckets of an [m, n] layer in full: 0 onehot_accum_kernel, 1 onehot_accum_w4_kernel.
+// GANQ_ACCUM_W4: 0 never, 1 wherever the four-wave kernel is supported, -1 by shape.
+bool accum_w4_supported(int64_t m, int64_t n) { return m >= 1 && n >= 256 && n % 256 == 0 && n <= 32768 && m * n < (1ll << 31); }
+int accum_plan(int64_t m, int64_t n) {
+    const long long opt = opt_get(OPT_ACCUM_W4);
+    if (opt == 0 || !accum_w4_supported(m, n)) return 0;
+    if (opt == 1) return 1;
+    // by shape (profiles/accum_w4_v1.txt, MI355X, V = 8): 0.91 x the first kernel's time at every in_features from 2048 to 14336
+    // (2048 .. 14336 rows), 0.95 x at 768 x 3072; level with it at 3072 x 768 (0.106 against 0.105 ms), so short rows stay
+    return n >= 2048 ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1507,8 +1833,10 @@ int t_iterate(const uint8_t* Q, int64_t m, int64_t n, int V, double rcond, const
     }
     GANQ_LAUNCH_CHECK();
     const size_t smem = 2 * (size_t)btile_bytes(4) + (size_t)TW * RW * 256 * sizeof(long long);  // (the extension's two planes need less)
+    const bool w4 = accum_plan(m, n) == 1;
     {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(onehot_accum_kernel), smem);
+        const int rc = w4 ? ensure_dynamic_lds(reinterpret_cast<const void*>(onehot_accum_w4_kernel), W4_LDS)
+                          : ensure_dynamic_lds(reinterpret_cast<const void*>(onehot_accum_kernel), smem);
         if (rc) return rc;
     }
     if (gated) {
@@ -1517,14 +1845,18 @@ int t_iterate(const uint8_t* Q, int64_t m, int64_t n, int V, double rcond, const
         const bool dbg = opt_get(OPT_ACCUM_DEBUG) == 1;  // developer timing experiment
         long long* stamps = nullptr;
         if (dbg) (void)hipMalloc(&stamps, 64);
-        hipLaunchKernelGGL(onehot_accum_kernel, dim3((unsigned)(2 * nrg * NP)), dim3(TW * 64), smem, stream, planes, bits, Q, (int)m, (int)n,
-                           (int)lo.nq, (int)lo.ng, mpart, mpart_lo, stamps, gate, thr, prep, nrg * NP);
+        if (w4)  // (32 rows per workgroup as well: the same grid)
+            hipLaunchKernelGGL(onehot_accum_w4_kernel, dim3((unsigned)(2 * nrg * NP)), dim3(256), W4_LDS, stream, planes, bits, Q, (int)m, (int)n,
+                               (int)lo.nq, (int)lo.ng, mpart, mpart_lo, stamps, gate, thr, prep, nrg * NP);
+        else
+            hipLaunchKernelGGL(onehot_accum_kernel, dim3((unsigned)(2 * nrg * NP)), dim3(TW * 64), smem, stream, planes, bits, Q, (int)m, (int)n,
+                               (int)lo.nq, (int)lo.ng, mpart, mpart_lo, stamps, gate, thr, prep, nrg * NP);
         if (stamps) {
             long long h[3];
             (void)hipStreamSynchronize(stream);
             (void)hipMemcpy(h, stamps, 24, hipMemcpyDeviceToHost);
             (void)hipFree(stamps);
-            fprintf(stderr, "[onehot_accum stamps] wg0 wave0: prologue %lld, tile loop %lld, flush %lld cycles\n", h[0], h[1], h[2]);
+            fprintf(stderr, "[onehot_accum%s stamps] wg0 wave0: prologue %lld, tile loop %lld, flush %lld cycles\n", w4 ? "_w4" : "", h[0], h[1], h[2]);
         }
         if (stateful) {
             hipLaunchKernelGGL(m_reduce_kernel, dim3(1024 + 256), dim3(256), 0, stream, mpart, mpart_lo, (int)m, mstate, mstate_lo, Q, qprev,
@@ -1592,6 +1924,15 @@ int t_active_rows(int64_t m, const TLayout& lo, char* ws, const int** list, cons
 }  // namespace ganq
 
 using namespace ganq;
+
+// tests: which kernel the full accumulation of an [m, n] layer takes under the current options (host only)
+extern "C" int ganq_debug_accum_plan(int64_t m, int64_t n, int* out) {
+    if (!out) return fail(-3, "ganq_debug_accum_plan: null pointer");
+    if (m <= 0 || n <= 0) return fail(-1, "ganq_debug_accum_plan: bad shape");
+    out[0] = accum_plan(m, n);
+    out[1] = accum_w4_supported(m, n) ? 1 : 0;
+    return 0;
+}
 
 // developer check (tests): the W @ H_fixed product of the fused driver and the fixed-point H it was formed with
 extern "C" int ganq_debug_wh_product(const float* W, const float* H, int64_t m, int64_t n, double* WH_out, double* Hfixed_out,

@@ -164,6 +164,11 @@ int ganq_debug_solve_plan(int active_tiles, int grid, int ncu, int* out);
  *            tiles a helper serves: tile, tile + 8, .. }. */
 int ganq_debug_solve_role(int active_tiles, int grid, int ncu, int cls, int ticket, int* out);
 
+/* which kernel sums the buckets of an [m, n] layer in full under the current developer options (host only, no device is asked):
+ * out[2] = { 0 onehot_accum_kernel / 1 onehot_accum_w4_kernel (four waves, LDS-DMA ring), 1 if the four-wave kernel supports the
+ * shape at all: in_features a multiple of 256 up to 32768, m n < 2^31 }.  GANQ_ACCUM_W4: -1 by shape, 0 never, 1 wherever supported. */
+int ganq_debug_accum_plan(int64_t m, int64_t n, int* out);
+
 /* ---- dense fp32 product C[m,n] = A[m,k] @ B[k,n] on the fp32 matrix cores (W@H, ganq.py:590) */
 int ganq_matmul_f32(const float* A, const float* B, int64_t m, int64_t k, int64_t n, float* C, void* stream);
 

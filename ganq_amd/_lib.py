@@ -55,6 +55,8 @@ SIGNATURES = {
     "ganq_solve_s_workspace_bytes": (_c_sz, [_c_i64, _c_i64, ctypes.c_int]),
     "ganq_debug_solve_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "ganq_debug_accum_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _c_vp]),
+    "ganq_debug_top_rule": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_longlong, ctypes.c_longlong, _c_vp]),
+    "ganq_debug_top_planes": (ctypes.c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp]),
     "ganq_debug_solve_role": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "ganq_solve_s": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp,
                                     _c_sz, _c_vp]),
@@ -734,6 +736,26 @@ def accum_plan(m: int, n: int) -> dict:
     out = (ctypes.c_int * 2)()
     _check(lib().ganq_debug_accum_plan(int(m), int(n), ctypes.cast(out, _c_vp)), "ganq_debug_accum_plan")
     return dict(kernel=ACCUM_KERNELS[out[0]], supported=bool(out[1]))
+
+
+def debug_top_rule(m: int, n: int, c3: int, c2: int) -> dict:
+    """how many digit planes of H the four-wave full bucket sum of an [m, n] layer multiplies when c3 / c2 entries have a non-zero
+    digit 3 / digit 2 or 3, under the current developer options (ganq_debug_top_rule; no GPU needed).  cap < 0: no list is wanted."""
+    out = (ctypes.c_int * 3)()
+    _check(lib().ganq_debug_top_rule(int(m), int(n), int(c3), int(c2), ctypes.cast(out, _c_vp)), "ganq_debug_top_rule")
+    return dict(D=out[0], cap=out[1], list_max=out[2])
+
+
+def debug_top_planes(H, m: int) -> dict:
+    """the exception counts of the fixed-point H [n,n] as the T-update's preparation forms them, and the number of dense digit
+    planes D of an [m, n] layer under the current developer options (ganq_debug_top_planes)"""
+    H = _dev_f32(H, "H")
+    n = H.shape[0]
+    if H.shape != (n, n):
+        raise GanqHipError(f"H must be square, got {tuple(H.shape)}")
+    out = (ctypes.c_longlong * 5)()
+    _call("ganq_debug_top_planes", (H,), H.data_ptr(), n, int(m), ctypes.cast(out, _c_vp), _ST)
+    return dict(c3=out[0], c2=out[1], cap=out[2], list_max=out[3], D=out[4])
 
 
 LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*

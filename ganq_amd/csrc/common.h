@@ -93,6 +93,8 @@ enum Opt : int {
     OPT_SOLVE_SHARE4_XB,
     OPT_SOLVE_CUS,
     OPT_ACCUM_W4,
+    OPT_T_TOP,
+    OPT_T_TOP_CAP,
     OPT_COUNT
 };
 long long opt_get(int id);

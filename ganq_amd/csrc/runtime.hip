@@ -73,6 +73,8 @@ const OptDesc kOpts[OPT_COUNT] = {
     {"GANQ_SOLVE_SHARE4_XB", 0},
     {"GANQ_SOLVE_CUS", 0},         // S-solve: > 0 = plan the helper regimes as if the chip had this many CUs (at most its own; tests)
     {"GANQ_ACCUM_W4", -1},         // T-update, full bucket sum: 1 = the four-wave kernel wherever it is supported (in_features a multiple of 256), 0 = never (-1: by shape, accum_plan in update_t.hip)
+    {"GANQ_T_TOP", -1},            // T-update, four-wave full bucket sum: 0 = always all four digit planes of H on the matrix cores (-1: only the planes that are not sparse, the rest from the exception lists of t_prepare)
+    {"GANQ_T_TOP_CAP", -1},        // ... entries an exception list may hold to be used (0: only an empty list; clamped to TOP_LIST_MAX; -1: the default of update_t.hip)
 };
 
 std::atomic<long long> g_opt[OPT_COUNT];

@@ -15,6 +15,8 @@ struct TLayout {
     // extension word of the fixed-point H (planes 4..5 live behind planes 0..3): its diagonal, its partial / kept bucket
     // sums, its int16 copy; per-feature exponents of the symmetric scaling used by the W @ H product
     size_t off_hdiag_j, off_mpart_lo, off_mstate_lo, off_jint, off_dexp, off_hdiag64;
+    // exception lists of the full bucket sum: the entries (u > v) with a non-zero digit 3 / a non-zero digit 2 or 3
+    size_t off_top3, off_top2;
 };
 
 TLayout t_layout(int64_t m, int64_t n, bool with_f64);

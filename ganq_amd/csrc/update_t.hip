@@ -78,7 +78,19 @@ struct TPrep {              // device-side header written by t_prepare
     double scale;           // H ~= scale * (I + J / 65536)
     unsigned int absmax_bits;
     int ext;                // 1: the 16-bit extension word J is in use (planes 4..5, Jint, the *_lo bucket sums)
+    // entries with u > v whose digit 3 / whose digit 2 or 3 is not zero (always exact), and how many of them a list may hold to be
+    // used instead of the dense planes (< 0: never; the lists hold the first top_cap entries counted)
+    unsigned int c3, c2;
+    int top_cap;
 };
+// capacity of either exception list (entries of 8 bytes): above it a plane is summed on the matrix cores whatever the cap asks for
+constexpr int TOP_LIST_MAX = 131072;
+// how many digit planes of the 31-bit word the four-wave kernel sums densely; the entries above them come from a list
+__host__ __device__ inline int top_dense_planes(long long c3, long long c2, long long cap) {
+    if (cap < 0) return 4;
+    if (c2 <= cap) return 2;
+    return c3 <= cap ? 3 : 4;
+}
 constexpr double EXT_UNIT = 1.0 / 65536.0;
 // two balanced base-256 digits hold J in [-32896, 32639]: the int16 copy stores J + JBIAS, which is exactly [-32768, 32767]
 constexpr int JBIAS = 128;
@@ -105,8 +117,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ H
 // scale = max|H| / 2^30; the extension word is switched on when the matrix has more dynamic range than one 31-bit
 // word serves: a bucket sum A[a][a] is about (n / V) mean(diag H), its rounding error about (n / V) 0.29 scale, so with
 // max|H| <= 16 mean(diag H) one word keeps A to 4e-9 relative -- beyond that the second word takes over.
-// ext_mode: -1 decide here, 0 never, 1 always (developer switch GANQ_H_EXT).
-__global__ __launch_bounds__(256) void prep_scale_kernel(const float* __restrict__ H, int n, TPrep* prep, int ext_mode) {
+// ext_mode: -1 decide here, 0 never, 1 always (developer switch GANQ_H_EXT).  top_cap: see TPrep (top_cap_in_force).
+__global__ __launch_bounds__(256) void prep_scale_kernel(const float* __restrict__ H, int n, TPrep* prep, int ext_mode, int top_cap) {
     __shared__ double sh[256];
     double s = 0.0;
     for (int u = threadIdx.x; u < n; u += 256) s += (double)H[(int64_t)u * n + u];
@@ -123,64 +135,137 @@ __global__ __launch_bounds__(256) void prep_scale_kernel(const float* __restrict
         const double mean_diag = sh[0] / (double)n;
         const bool wide = ok && !((double)mx <= 16.0 * mean_diag);  // also for a non-positive / NaN mean
         prep->ext = ext_mode < 0 ? (wide ? 1 : 0) : (ext_mode ? 1 : 0);
+        prep->top_cap = top_cap;
     }
 }
 
 // planes[p][v][u] (row pitch nq, zero padded; p = 0..3 digits of I, p = 4..5 digits of J), hdiag_int[u] / hdiag_j[u],
-// optionally H64[v][u] = scale * (I + J / 65536), Hint = I (int32), Jint = J (int16)
-__global__ __launch_bounds__(256) void hquant_kernel(const float* __restrict__ H, int n, int nq, const TPrep* __restrict__ prep,
+// optionally H64[v][u] = scale * (I + J / 65536), Hint = I (int32), Jint = J (int16).
+// The entries with u > v (the bytes the full sum reads) whose top digits are not zero are counted in prep->c3 / c2 and, while a list
+// has room (prep->top_cap), appended to it as (u | v << 16, value): top3 holds d3, top2 holds d2 + 256 d3.  A workgroup quantises
+// `tiles` runs of 1024 entries and collects its list entries in LDS: one atomic on a counter per HQ_BUF / 2 entries or more, and none
+// but a last one once a list is known to overflow (thousands of same-address atomics are what absmax and q_diff had to get rid of).
+constexpr int HQ_BUF = 2048;  // entries per list a workgroup holds back; a tile adds at most 1024
+__global__ __launch_bounds__(256) void hquant_kernel(const float* __restrict__ H, int n, int nq, TPrep* __restrict__ prep,
                                                     int8_t* __restrict__ planes, int* __restrict__ hdiag_int,
                                                     int* __restrict__ hdiag_j, double* __restrict__ H64,
-                                                    int* __restrict__ Hint, short* __restrict__ Jint) {
-    const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;  // 4 consecutive u of one row v
+                                                    int* __restrict__ Hint, short* __restrict__ Jint, uint2* __restrict__ top3,
+                                                    uint2* __restrict__ top2, int tiles) {
+    __shared__ uint2 buf[2][HQ_BUF];
+    __shared__ unsigned int fill[2], base_sh[2], late[2];
+    const int tid = threadIdx.x;
+    if (tid < 2) fill[tid] = late[tid] = 0;
+    __syncthreads();
     const int64_t per_row = nq;
-    if (i4 >= (int64_t)n * per_row) return;
-    const int v = (int)(i4 / per_row), u0 = (int)(i4 % per_row);
+    const int64_t total = (int64_t)n * per_row;
     const double scale = prep->scale;
     const bool ext = prep->ext != 0;
+    const int cap = prep->top_cap;
     const double inv = scale > 0.0 ? 1.0 / scale : 0.0;
-    uint32_t pk[6] = {0, 0, 0, 0, 0, 0};
+    bool full[2] = {cap < 0, cap < 0};  // (uniform) nothing more is stored in this list: it overflows, or no list is wanted
+    unsigned int mine[2] = {0, 0};      // counted, not stored
+    // everybody, behind a barrier: the f entries held back go to their place in the list, as far as it has room
+    auto flush = [&](int l, unsigned int f) {
+        if (tid == 0) base_sh[l] = atomicAdd(l ? &prep->c2 : &prep->c3, f);
+        __syncthreads();
+        const unsigned int base = base_sh[l];
+        uint2* list = l ? top2 : top3;
+        for (unsigned int i = tid; i < f; i += 256)
+            if (base + i < (unsigned int)cap) list[base + i] = buf[l][i];
+        if (base + f > (unsigned int)cap) full[l] = true;
+        __syncthreads();
+        if (tid == 0) fill[l] = 0;
+        __syncthreads();
+    };
+    for (int t = 0; t < tiles; ++t) {
+        const int64_t tile0 = ((int64_t)blockIdx.x * tiles + t) * 1024;
+        if (tile0 >= total) break;
+        const int64_t i4 = tile0 + 4 * tid;  // 4 consecutive u of one row v
+        uint32_t euv[4] = {0, 0, 0, 0};
+        int ev[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        if (i4 < total) {
+            const int v = (int)(i4 / per_row), u0 = (int)(i4 % per_row);
+            uint32_t pk[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int u = u0 + k;
-        int xi = 0, xj = 0;
-        if (u < n) {
-            const double x = fmin(fmax((double)H[(int64_t)v * n + u] * inv, -1073741824.0), 1073741824.0);
-            xi = (int)__builtin_rint(x);
-            if (ext) {
-                // remainder in units of 2^-16: two balanced base-256 digits hold [-32896, 32639]
-                xj = (int)__builtin_rint((x - (double)xi) * 65536.0);
-                if (xj > 32639) {
-                    xi += 1;
-                    xj -= 65536;
+            for (int k = 0; k < 4; ++k) {
+                const int u = u0 + k;
+                int xi = 0, xj = 0;
+                if (u < n) {
+                    const double x = fmin(fmax((double)H[(int64_t)v * n + u] * inv, -1073741824.0), 1073741824.0);
+                    xi = (int)__builtin_rint(x);
+                    if (ext) {
+                        // remainder in units of 2^-16: two balanced base-256 digits hold [-32896, 32639]
+                        xj = (int)__builtin_rint((x - (double)xi) * 65536.0);
+                        if (xj > 32639) {
+                            xi += 1;
+                            xj -= 65536;
+                        }
+                    }
+                    if (H64) H64[(int64_t)v * n + u] = scale * ((double)xi + (double)xj * EXT_UNIT);
+                    if (Hint) Hint[(int64_t)v * n + u] = xi;
+                    if (Jint) Jint[(int64_t)v * n + u] = (short)(xj + JBIAS);
+                    if (u == v) {
+                        hdiag_int[u] = xi;
+                        hdiag_j[u] = xj;
+                    }
+                }
+                int r = xi;
+                int dg[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {  // balanced base-256 digits: r = d + 256 * r', d in [-128, 127]
+                    const int d = ((r + 128) & 255) - 128;
+                    r = (r - d) >> 8;
+                    pk[p] |= (uint32_t)(d & 255) << (8 * k);
+                    dg[p] = d;
+                }
+                if (u < n && u > v) {
+                    euv[k] = (uint32_t)u | ((uint32_t)v << 16);
+                    ev[0][k] = dg[3];
+                    ev[1][k] = dg[2] + 256 * dg[3];  // zero only when both digits are
+                }
+                r = xj;
+#pragma unroll
+                for (int p = 4; p < 6; ++p) {
+                    const int d = ((r + 128) & 255) - 128;
+                    r = (r - d) >> 8;
+                    pk[p] |= (uint32_t)(d & 255) << (8 * k);
                 }
             }
-            if (H64) H64[(int64_t)v * n + u] = scale * ((double)xi + (double)xj * EXT_UNIT);
-            if (Hint) Hint[(int64_t)v * n + u] = xi;
-            if (Jint) Jint[(int64_t)v * n + u] = (short)(xj + JBIAS);
-            if (u == v) {
-                hdiag_int[u] = xi;
-                hdiag_j[u] = xj;
+#pragma unroll
+            for (int p = 0; p < 6; ++p)
+                if (p < 4 || ext) *reinterpret_cast<uint32_t*>(planes + ((int64_t)p * n + v) * nq + u0) = pk[p];
+        }
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+            unsigned int cnt = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) cnt += ev[l][k] != 0;
+            if (full[l]) mine[l] += cnt;
+            else if (cnt) {
+                unsigned int s = atomicAdd(&fill[l], cnt);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (ev[l][k] != 0) buf[l][s++] = make_uint2(euv[k], (uint32_t)ev[l][k]);
             }
         }
-        int r = xi;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {  // balanced base-256 digits: r = d + 256 * r', d in [-128, 127]
-            const int d = ((r + 128) & 255) - 128;
-            r = (r - d) >> 8;
-            pk[p] |= (uint32_t)(d & 255) << (8 * k);
-        }
-        r = xj;
-#pragma unroll
-        for (int p = 4; p < 6; ++p) {
-            const int d = ((r + 128) & 255) - 128;
-            r = (r - d) >> 8;
-            pk[p] |= (uint32_t)(d & 255) << (8 * k);
-        }
+        if (full[0] && full[1]) continue;
+        __syncthreads();
+        const unsigned int f0 = fill[0], f1 = fill[1];
+        __syncthreads();  // (nobody adds to this tile's fill counts before everybody has read them)
+        if (!full[0] && f0 > HQ_BUF - 1024) flush(0, f0);
+        if (!full[1] && f1 > HQ_BUF - 1024) flush(1, f1);
     }
+    __syncthreads();
 #pragma unroll
-    for (int p = 0; p < 6; ++p)
-        if (p < 4 || ext) *reinterpret_cast<uint32_t*>(planes + ((int64_t)p * n + v) * nq + u0) = pk[p];
+    for (int l = 0; l < 2; ++l) {
+        const unsigned int f = fill[l];  // (uniform: behind a barrier, and flush ends with one)
+        if (!full[l] && f) flush(l, f);
+        unsigned int c = mine[l];
+        for (int off = 32; off > 0; off >>= 1) c += (unsigned int)__shfl_xor((int)c, off);
+        if ((tid & 63) == 0 && c) atomicAdd(&late[l], c);
+    }
+    __syncthreads();
+    if (tid < 2 && late[tid]) atomicAdd(tid ? &prep->c2 : &prep->c3, late[tid]);
 }
 
 // per-feature exponents for the W @ H product: e[u] = floor(log2(H_uu) / 2), so that H~[u][v] = H[u][v] 2^(-e_u - e_v) has a
@@ -508,7 +593,8 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     if (P0 != 0 && prep->ext == 0) return;
     constexpr int ST = NPL * 32 * W4_SU;  // bytes per stage
     constexpr int NI = ST / 1024 / 4;     // LDS-DMA instructions (64 lanes x 16 B) per wave and slice
-    constexpr int HSTEP = 4 / NI;         // ... one in front of every HSTEP-th half
+    constexpr int HSTEP = 4 / NI;         // ... one in front of every HSTEP-th half (three planes: of the first three halves)
+    static_assert(NPL >= 2 && NPL <= 4 && NI * 4 * 1024 == ST && NI * HSTEP <= 4, "a slice is NI LDS-DMA instructions per wave");
     extern __shared__ __align__(1024) char w4_smem[];
     char* const ring = w4_smem;
     long long(*Mrow)[8][256] = reinterpret_cast<long long(*)[8][256]>(w4_smem + W4_RING);  // [wave][row][a * 16 + b]
@@ -550,6 +636,8 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     auto wait_masks = [&]() {
         if constexpr (NI == 4)
             asm volatile("s_waitcnt vmcnt(4)" : "+v"(wn[0][0]), "+v"(wn[0][1]), "+v"(wn[0][2]), "+v"(wn[0][3]), "+v"(wn[1][0]), "+v"(wn[1][1]), "+v"(wn[1][2]), "+v"(wn[1][3]) : : "memory");
+        else if constexpr (NI == 3)
+            asm volatile("s_waitcnt vmcnt(3)" : "+v"(wn[0][0]), "+v"(wn[0][1]), "+v"(wn[0][2]), "+v"(wn[0][3]), "+v"(wn[1][0]), "+v"(wn[1][1]), "+v"(wn[1][2]), "+v"(wn[1][3]) : : "memory");
         else
             asm volatile("s_waitcnt vmcnt(2)" : "+v"(wn[0][0]), "+v"(wn[0][1]), "+v"(wn[0][2]), "+v"(wn[0][3]), "+v"(wn[1][0]), "+v"(wn[1][1]), "+v"(wn[1][2]), "+v"(wn[1][3]) : : "memory");
     };
@@ -562,6 +650,8 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     auto wait_codes = [&]() {
         if constexpr (NI == 4)
             asm volatile("s_waitcnt vmcnt(4)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+        else if constexpr (NI == 3)
+            asm volatile("s_waitcnt vmcnt(3)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
         else
             asm volatile("s_waitcnt vmcnt(2)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
     };
@@ -653,7 +743,7 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 auto feed = [&]() {  // this half's share of the slice's LDS-DMA; the B fragments of the next half / slice
-                    if (h % HSTEP == 0) dma(iss, (f + 3) & 3, h / HSTEP);
+                    if (h % HSTEP == 0 && h / HSTEP < NI) dma(iss, (f + 3) & 3, h / HSTEP);
                     if (h < 3) read_b(stage, h + 1, bf[(h + 1) & 1]);
                     else read_b((f + 1) & 3, 0, bf[0]);
                 };
@@ -704,6 +794,8 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
         for (int p = 0; p < 4; ++p) {
             if constexpr (NPL == 4)
                 asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]), "+a"(acc[p][2]), "+a"(acc[p][3]));
+            else if constexpr (NPL == 3)
+                asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]), "+a"(acc[p][2]));
             else asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]));
         }
         const uint32_t mrow0 = (uint32_t)(uintptr_t)&Mrow[wv][0][0];
@@ -717,6 +809,7 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
                 // them per chunk cost more than the additions they saved): a code outside 0 .. 15 adds zero to bucket b & 15
                 long long val = (long long)(acc[p][0][reg] + (acc[p][1][reg] << 8));
                 if constexpr (NPL == 4) val += (long long)(acc[p][2][reg] + (acc[p][3][reg] << 8)) << 16;
+                if constexpr (NPL == 3) val += (long long)acc[p][2][reg] << 16;
                 const uint32_t b = h ? bq[2 * p + 1] : bq[2 * p];
                 if (b >= 16u) val = 0;
                 w4_lds_add_u64(mrow0 + (uint32_t)((((2 * p + h) * 16 + a) * 16 + (b & 15u)) * 8), (unsigned long long)val);
@@ -739,7 +832,8 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
         }
 }
 
-// one launch for both words, as onehot_accum_kernel
+// one launch for both words, as onehot_accum_kernel.  The 31-bit word: as many digit planes as top_dense_planes says, one choice for
+// the whole launch (top_fixup_kernel adds what lies above them)
 __global__ __launch_bounds__(256, 1) void onehot_accum_w4_kernel(const int8_t* __restrict__ planes_all,
                                                                 const unsigned long long* __restrict__ bits,
                                                                 const uint8_t* __restrict__ Q, int m, int n, int nq, int ng,
@@ -747,8 +841,12 @@ __global__ __launch_bounds__(256, 1) void onehot_accum_w4_kernel(const int8_t* _
                                                                 long long* __restrict__ stamps, const long long* __restrict__ changed,
                                                                 long long thr, const TPrep* __restrict__ prep, int nblk_hi) {
     if (changed && *changed <= thr) return;
-    if ((int)blockIdx.x < nblk_hi) accum_w4_body<4, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
-    else accum_w4_body<2, 4>(planes_all, bits, Q, m, n, nq, ng, Mpart_lo, nullptr, prep, (int)blockIdx.x - nblk_hi);
+    if ((int)blockIdx.x < nblk_hi) {
+        const int D = top_dense_planes(prep->c3, prep->c2, prep->top_cap);
+        if (D == 2) accum_w4_body<2, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
+        else if (D == 3) accum_w4_body<3, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
+        else accum_w4_body<4, 0>(planes_all, bits, Q, m, n, nq, ng, Mpart_hi, stamps, prep, (int)blockIdx.x);
+    } else accum_w4_body<2, 4>(planes_all, bits, Q, m, n, nq, ng, Mpart_lo, nullptr, prep, (int)blockIdx.x - nblk_hi);
 }
 
 // which kernel sums the buckets of an [m, n] layer in full: 0 onehot_accum_kernel, 1 onehot_accum_w4_kernel.
@@ -761,6 +859,49 @@ int accum_plan(int64_t m, int64_t n) {
     // by shape (profiles/accum_w4_v1.txt, MI355X, V = 8): 0.91 x the first kernel's time at every in_features from 2048 to 14336
     // (2048 .. 14336 rows), 0.95 x at 768 x 3072; level with it at 3072 x 768 (0.106 against 0.105 ms), so short rows stay
     return n >= 2048 ? 1 : 0;
+}
+
+// the cap on the exception lists of an [m, n] layer: < 0 when no list is wanted (the first kernel sums the layer, or GANQ_T_TOP=0).
+// GANQ_T_TOP_CAP overrides the default; TOP_LIST_MAX bounds both.
+// The default grows with n^2, as the plane it saves does: a dense plane costs every row n^2 / 2 multiply-adds, a list entry one LDS
+// atomic per row, so the break-even count is a fixed share of the pairs whatever m is.
+constexpr int TOP_CAP_SHARE = 1024;  // default cap = n^2 / TOP_CAP_SHARE
+int top_cap_in_force(int64_t m, int64_t n) {
+    if (accum_plan(m, n) != 1 || opt_get(OPT_T_TOP) == 0) return -1;
+    const long long c = opt_get(OPT_T_TOP_CAP);
+    return (int)std::min<long long>(c < 0 ? n * n / TOP_CAP_SHARE : c, TOP_LIST_MAX);
+}
+
+// What onehot_accum_w4_kernel left out when it summed D < 4 planes: sum of `value` over the list's entries (u, v) into bucket
+// [Q[row][u]][Q[row][v]], times 2^(8 D), added to part 0 of the row's partial sums.  One workgroup per row: the row's codes and 256
+// 64-bit buckets in LDS, the threads stride the list (the same list for every row: it stays in L2).  Integers: exact in any order.
+__global__ __launch_bounds__(256) void top_fixup_kernel(const uint2* __restrict__ top3, const uint2* __restrict__ top2,
+                                                       const uint8_t* __restrict__ Q, int m, int n, long long* __restrict__ Mpart,
+                                                       const long long* __restrict__ changed, long long thr,
+                                                       const TPrep* __restrict__ prep) {
+    if (changed && *changed <= thr) return;
+    const int D = top_dense_planes(prep->c3, prep->c2, prep->top_cap);
+    if (D == 4) return;
+    const unsigned int cnt = D == 2 ? prep->c2 : prep->c3;  // (<= top_cap <= TOP_LIST_MAX: the whole list was stored)
+    if (cnt == 0) return;
+    const uint2* __restrict__ list = D == 2 ? top2 : top3;
+    extern __shared__ __align__(16) char fx_smem[];
+    long long* bucket = reinterpret_cast<long long*>(fx_smem);  // [a * 16 + b]
+    uint8_t* codes = reinterpret_cast<uint8_t*>(fx_smem) + 256 * sizeof(long long);
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const uint8_t* q = Q + (int64_t)row * n;
+    bucket[tid] = 0;
+    for (int x = tid; x < n; x += 256) codes[x] = q[x];
+    __syncthreads();
+    for (unsigned int i = tid; i < cnt; i += 256) {
+        const uint2 e = list[i];
+        const uint32_t a = codes[e.x & 0xffffu], b = codes[e.x >> 16];  // a from u, b from v, as the dense kernel
+        if (a < 16u && b < 16u)
+            __hip_atomic_fetch_add(&bucket[a * 16 + b], (long long)(int)e.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    const long long add = bucket[tid];
+    if (add) Mpart[(int64_t)row * 256 + tid] += add * (1ll << (8 * D));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1661,6 +1802,8 @@ TLayout t_layout(int64_t m, int64_t n, bool with_f64) {
     lo.off_bits = take((size_t)m * lo.ng * 16 * sizeof(unsigned long long));
     lo.off_mpart = take((size_t)NP * m * 256 * sizeof(long long));
     lo.off_mpart_lo = take((size_t)NP * m * 256 * sizeof(long long));
+    lo.off_top3 = take((size_t)TOP_LIST_MAX * sizeof(uint2));  // exception lists: entries with a non-zero digit 3 / digit 2 or 3
+    lo.off_top2 = take((size_t)TOP_LIST_MAX * sizeof(uint2));
     lo.off_mstate_lo = lo.off_jint = lo.off_dexp = lo.off_hdiag64 = 0;
     lo.off_h64 = lo.off_wh64 = lo.off_whw = lo.off_lossrows = 0;
     lo.off_hint = lo.off_qprev = lo.off_mstate = lo.off_chg = lo.off_chgcnt = 0;
@@ -1741,12 +1884,15 @@ int t_prepare(const float* W, const float* H, int64_t m, int64_t n, const TLayou
     ProfScope prof(KID_T_PREP, stream);
     GANQ_HIP_CHECK(hipMemsetAsync(prep, 0, sizeof(TPrep), stream));
     hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, stream, H, n * n, prep);
-    hipLaunchKernelGGL(prep_scale_kernel, dim3(1), dim3(256), 0, stream, H, (int)n, prep, (int)opt_get(OPT_H_EXT));
-    const int64_t quads = n * lo.nq / 4;
+    hipLaunchKernelGGL(prep_scale_kernel, dim3(1), dim3(256), 0, stream, H, (int)n, prep, (int)opt_get(OPT_H_EXT), top_cap_in_force(m, n));
+    // runs of 1024 entries per workgroup: as many as leave about a thousand workgroups, 16 at the most
+    const int64_t htiles = (n * lo.nq + 1023) / 1024;
+    const int per_wg = (int)std::min<int64_t>(16, std::max<int64_t>(1, htiles / 1024));
     int* Hint = with_f64 ? reinterpret_cast<int*>(ws + lo.off_hint) : nullptr;
     short* Jint = with_f64 ? reinterpret_cast<short*>(ws + lo.off_jint) : nullptr;
-    hipLaunchKernelGGL(hquant_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, H, (int)n, (int)lo.nq, prep,
-                       planes, hdiag, hdiag_j, H64, Hint, Jint);
+    hipLaunchKernelGGL(hquant_kernel, dim3((unsigned)((htiles + per_wg - 1) / per_wg)), dim3(256), 0, stream, H, (int)n, (int)lo.nq, prep,
+                       planes, hdiag, hdiag_j, H64, Hint, Jint, reinterpret_cast<uint2*>(ws + lo.off_top3),
+                       reinterpret_cast<uint2*>(ws + lo.off_top2), per_wg);
     GANQ_LAUNCH_CHECK();
     if (with_f64) {
         // change counter of the incremental bucket sums: zero once, every t_solve leaves it zero again
@@ -1845,10 +1991,14 @@ int t_iterate(const uint8_t* Q, int64_t m, int64_t n, int V, double rcond, const
         const bool dbg = opt_get(OPT_ACCUM_DEBUG) == 1;  // developer timing experiment
         long long* stamps = nullptr;
         if (dbg) (void)hipMalloc(&stamps, 64);
-        if (w4)  // (32 rows per workgroup as well: the same grid)
+        if (w4) {  // (32 rows per workgroup as well: the same grid)
             hipLaunchKernelGGL(onehot_accum_w4_kernel, dim3((unsigned)(2 * nrg * NP)), dim3(256), W4_LDS, stream, planes, bits, Q, (int)m, (int)n,
                                (int)lo.nq, (int)lo.ng, mpart, mpart_lo, stamps, gate, thr, prep, nrg * NP);
-        else
+            // the digit planes it left to the lists (leaves at once when it summed all four)
+            hipLaunchKernelGGL(top_fixup_kernel, dim3((unsigned)m), dim3(256), 256 * sizeof(long long) + (size_t)n, stream,
+                               reinterpret_cast<const uint2*>(ws + lo.off_top3), reinterpret_cast<const uint2*>(ws + lo.off_top2), Q, (int)m,
+                               (int)n, mpart, gate, thr, prep);
+        } else
             hipLaunchKernelGGL(onehot_accum_kernel, dim3((unsigned)(2 * nrg * NP)), dim3(TW * 64), smem, stream, planes, bits, Q, (int)m, (int)n,
                                (int)lo.nq, (int)lo.ng, mpart, mpart_lo, stamps, gate, thr, prep, nrg * NP);
         if (stamps) {
@@ -1931,6 +2081,45 @@ extern "C" int ganq_debug_accum_plan(int64_t m, int64_t n, int* out) {
     if (m <= 0 || n <= 0) return fail(-1, "ganq_debug_accum_plan: bad shape");
     out[0] = accum_plan(m, n);
     out[1] = accum_w4_supported(m, n) ? 1 : 0;
+    return 0;
+}
+
+// tests: how many digit planes the four-wave kernel would sum densely for an [m, n] layer whose H has c3 / c2 exceptions, under the
+// current options (host only: top_dense_planes is the function the kernels evaluate).  out: D, the cap in force, TOP_LIST_MAX
+extern "C" int ganq_debug_top_rule(int64_t m, int64_t n, long long c3, long long c2, int* out) {
+    if (!out) return fail(-3, "ganq_debug_top_rule: null pointer");
+    if (m <= 0 || n <= 0 || c3 < 0 || c2 < c3) return fail(-1, "ganq_debug_top_rule: bad shape / counts");
+    const int cap = top_cap_in_force(m, n);
+    out[0] = top_dense_planes(c3, c2, cap);
+    out[1] = cap;
+    out[2] = TOP_LIST_MAX;
+    return 0;
+}
+
+// tests, sweeps: the exception counts of H as t_prepare forms them for an [m, n] layer.  out (host, 5 values): c3, c2, the cap in
+// force (< 0: no list is wanted), TOP_LIST_MAX, D
+extern "C" int ganq_debug_top_planes(const float* H, int64_t n, int64_t m, long long* out, void* stream_) {
+    if (!H || !out) return fail(-3, "ganq_debug_top_planes: null pointer");
+    if (m <= 0 || n <= 0 || m > INT32_MAX / 2 || n > INT32_MAX / 2) return fail(-1, "ganq_debug_top_planes: bad shape");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const TLayout lo = t_layout(m, n, false);
+    char* ws = nullptr;
+    GANQ_HIP_CHECK(hipMalloc(&ws, lo.total));
+    int rc = t_prepare(nullptr, H, m, n, lo, ws, false, stream);
+    TPrep h;
+    if (rc == 0) {
+        hipError_t e = hipMemcpyAsync(&h, ws + lo.off_prep, sizeof(TPrep), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) rc = fail(-4, "ganq_debug_top_planes: %s", hipGetErrorString(e));
+    }
+    if (rc != 0) (void)hipDeviceSynchronize();
+    (void)hipFree(ws);
+    if (rc) return rc;
+    out[0] = h.c3;
+    out[1] = h.c2;
+    out[2] = h.top_cap;
+    out[3] = TOP_LIST_MAX;
+    out[4] = top_dense_planes(h.c3, h.c2, h.top_cap);
     return 0;
 }
 

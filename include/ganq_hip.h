@@ -168,6 +168,15 @@ int ganq_debug_solve_role(int active_tiles, int grid, int ncu, int cls, int tick
  * out[2] = { 0 onehot_accum_kernel / 1 onehot_accum_w4_kernel (four waves, LDS-DMA ring), 1 if the four-wave kernel supports the
  * shape at all: in_features a multiple of 256 up to 32768, m n < 2^31 }.  GANQ_ACCUM_W4: -1 by shape, 0 never, 1 wherever supported. */
 int ganq_debug_accum_plan(int64_t m, int64_t n, int* out);
+/* The four-wave kernel sums only the D lowest digit planes of the fixed-point H that are not sparse; the entries (u > v) with a
+ * non-zero digit 3 (c3 of them) or a non-zero digit 2 or 3 (c2) come from exception lists that the preparation fills:
+ * D = 2 if c2 <= cap, else 3 if c3 <= cap, else 4.  GANQ_T_TOP: -1 as described, 0 always D = 4.  GANQ_T_TOP_CAP: the cap (-1: the
+ * built-in default; clamped to the lists' capacity).  The rule alone, host only: out[3] = { D, cap in force (< 0: no list is wanted:
+ * GANQ_T_TOP=0 or the layer takes the first kernel), capacity of a list }. */
+int ganq_debug_top_rule(int64_t m, int64_t n, long long c3, long long c2, int* out);
+/* ... and on the device: the quantisation of the preparation for H [n,n] (device) of an [m, n] layer.
+ * out[5] (host) = { c3, c2, cap in force, capacity of a list, D }. */
+int ganq_debug_top_planes(const float* H, int64_t n, int64_t m, long long* out, void* stream);
 
 /* ---- dense fp32 product C[m,n] = A[m,k] @ B[k,n] on the fp32 matrix cores (W@H, ganq.py:590) */
 int ganq_matmul_f32(const float* A, const float* B, int64_t m, int64_t k, int64_t n, float* C, void* stream);

@@ -57,6 +57,7 @@ SIGNATURES = {
     "ganq_debug_accum_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _c_vp]),
     "ganq_debug_top_rule": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_longlong, ctypes.c_longlong, _c_vp]),
     "ganq_debug_top_planes": (ctypes.c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp]),
+    "ganq_debug_mu_planes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_longlong, ctypes.c_longlong, _c_vp]),
     "ganq_debug_solve_role": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "ganq_solve_s": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp,
                                     _c_sz, _c_vp]),
@@ -756,6 +757,14 @@ def debug_top_planes(H, m: int) -> dict:
     out = (ctypes.c_longlong * 5)()
     _call("ganq_debug_top_planes", (H,), H.data_ptr(), n, int(m), ctypes.cast(out, _c_vp), _ST)
     return dict(c3=out[0], c2=out[1], cap=out[2], list_max=out[3], D=out[4])
+
+
+def debug_mu_planes(m: int, n: int, c3: int, c2: int) -> dict:
+    """how many digit planes of H the incremental bucket sums of an [m, n] layer read on the matrix cores when c3 / c2 entries have
+    a non-zero digit 3 / digit 2 or 3, under the current developer options (ganq_debug_mu_planes; no GPU needed); D_full: the full sum's"""
+    out = (ctypes.c_int * 2)()
+    _check(lib().ganq_debug_mu_planes(int(m), int(n), int(c3), int(c2), ctypes.cast(out, _c_vp)), "ganq_debug_mu_planes")
+    return dict(D=out[0], D_full=out[1])
 
 
 LUT_REGIMES = ("decode16", "decode32", "mfma_small", "gemm", "gemm_splitk", "gemm_pipe", "dense128", "dense256")  # GANQ_LUT_REGIME_*

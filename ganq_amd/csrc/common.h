@@ -95,6 +95,7 @@ enum Opt : int {
     OPT_ACCUM_W4,
     OPT_T_TOP,
     OPT_T_TOP_CAP,
+    OPT_MU_TOP,
     OPT_COUNT
 };
 long long opt_get(int id);

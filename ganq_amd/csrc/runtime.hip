@@ -75,6 +75,7 @@ const OptDesc kOpts[OPT_COUNT] = {
     {"GANQ_ACCUM_W4", -1},         // T-update, full bucket sum: 1 = the four-wave kernel wherever it is supported (in_features a multiple of 256), 0 = never (-1: by shape, accum_plan in update_t.hip)
     {"GANQ_T_TOP", -1},            // T-update, four-wave full bucket sum: 0 = always all four digit planes of H on the matrix cores (-1: only the planes that are not sparse, the rest from the exception lists of t_prepare)
     {"GANQ_T_TOP_CAP", -1},        // ... entries an exception list may hold to be used (0: only an empty list; clamped to TOP_LIST_MAX; -1: the default of update_t.hip)
+    {"GANQ_MU_TOP", -1},           // T-update, incremental bucket sums on the matrix cores: 0 = always read all four digit planes of H; -1: the planes the full sum takes, the rest from the per-column index of the exception list; 3 (A/B): those, but at least three
 };
 
 std::atomic<long long> g_opt[OPT_COUNT];

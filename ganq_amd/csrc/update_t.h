@@ -17,6 +17,8 @@ struct TLayout {
     size_t off_hdiag_j, off_mpart_lo, off_mstate_lo, off_jint, off_dexp, off_hdiag64;
     // exception lists of the full bucket sum: the entries (u > v) with a non-zero digit 3 / a non-zero digit 2 or 3
     size_t off_top3, off_top2;
+    // per-column index of the list in force for the incremental sums (loop driver only): n + 1 offsets, the entries filed under both ends
+    size_t off_topoff, off_topent;
 };
 
 TLayout t_layout(int64_t m, int64_t n, bool with_f64);

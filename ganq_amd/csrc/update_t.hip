@@ -82,6 +82,7 @@ struct TPrep {              // device-side header written by t_prepare
     // used instead of the dense planes (< 0: never; the lists hold the first top_cap entries counted)
     unsigned int c3, c2;
     int top_cap;
+    int mu_index;           // the D top_index_kernel built the per-column index for (0: it did not run; 4: nothing to index)
 };
 // capacity of either exception list (entries of 8 bytes): above it a plane is summed on the matrix cores whatever the cap asks for
 constexpr int TOP_LIST_MAX = 131072;
@@ -90,6 +91,20 @@ __host__ __device__ inline int top_dense_planes(long long c3, long long c2, long
     if (cap < 0) return 4;
     if (c2 <= cap) return 2;
     return c3 <= cap ? 3 : 4;
+}
+// ... and how many m_update_mfma_kernel reads (mu_top = GANQ_MU_TOP): the same ones; 0: all four; 3 (A/B): the same ones but never
+// fewer than three.  Where the full sum takes two planes, c3 <= c2 <= cap: the list of the entries above digit 2 is complete as well.
+__host__ __device__ inline int mu_dense_planes(long long c3, long long c2, long long cap, int mu_top) {
+    if (mu_top == 0) return 4;
+    const int d = top_dense_planes(c3, c2, cap);
+    return d == 2 && mu_top == 3 ? 3 : d;
+}
+// the value of the D lowest balanced base-256 digits of a 31-bit word x (hquant_kernel's digits): the residue of x modulo 256^D in
+// [-B, 256^D - 1 - B], B = 0x80 in each of the D bytes
+__host__ __device__ inline long long low_digits(long long x, int D) {
+    if (D >= 4) return x;
+    const long long B = D == 3 ? 0x808080ll : 0x8080ll;
+    return ((x + B) & ((1ll << (8 * D)) - 1)) - B;
 }
 constexpr double EXT_UNIT = 1.0 / 65536.0;
 // two balanced base-256 digits hold J in [-32896, 32639]: the int16 copy stores J + JBIAS, which is exactly [-32768, 32767]
@@ -904,6 +919,61 @@ __global__ __launch_bounds__(256) void top_fixup_kernel(const uint2* __restrict_
     if (add) Mpart[(int64_t)row * 256 + tid] += add * (1ll << (8 * D));
 }
 
+// Per-column index of the exception list that goes with the D = mu_dense_planes(..) planes of the incremental sums, once per layer: a
+// changed column c must find the listed pairs it is an end of without scanning the list.  Entry (u, v, value) is filed under u as
+// (v, value) and under v as (u, value); col_off[c] .. col_off[c + 1] bound column c's run of col_ent (at most 2 TOP_LIST_MAX entries).
+// One workgroup: counts, offsets and cursors live in LDS (n + 1 ints, n <= 32768), so a massive column's thousands of increments
+// are LDS atomics on one address and not global ones.  The order inside a run depends on the scheduling; the sums formed from it are
+// integers.  Leaves at once when all four planes are dense or the list is empty (the consumer then reads nothing).
+__global__ __launch_bounds__(1024) void top_index_kernel(const uint2* __restrict__ top3, const uint2* __restrict__ top2,
+                                                        TPrep* __restrict__ prep, int n, int* __restrict__ col_off,
+                                                        uint2* __restrict__ col_ent, int mu_top) {
+    const int D = mu_dense_planes(prep->c3, prep->c2, prep->top_cap, mu_top);
+    if (threadIdx.x == 0) prep->mu_index = D;  // (also when nothing is filed below: the consumer then reads nothing)
+    if (D == 4) return;
+    const unsigned int cnt = D == 2 ? prep->c2 : prep->c3;  // (<= top_cap <= TOP_LIST_MAX: the whole list was stored)
+    if (cnt == 0) return;
+    const uint2* __restrict__ list = D == 2 ? top2 : top3;
+    extern __shared__ int ti_cur[];  // [n]: counts, then cursors
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int c = tid; c < n; c += 1024) ti_cur[c] = 0;
+    __syncthreads();
+    for (unsigned int i = tid; i < cnt; i += 1024) {
+        const uint32_t uv = list[i].x;
+        atomicAdd(&ti_cur[uv & 0xffffu], 1);
+        atomicAdd(&ti_cur[uv >> 16], 1);
+    }
+    __syncthreads();
+    // exclusive scan: thread t owns columns t per .. t per + per - 1
+    const int per = (n + 1023) / 1024, c0 = min(tid * per, n), c1 = min(c0 + per, n);
+    int mine = 0;
+    for (int c = c0; c < c1; ++c) mine += ti_cur[c];
+    int incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int run = incl - mine;
+    for (int k = 0; k < wv; ++k) run += wsum[k];
+    for (int c = c0; c < c1; ++c) {
+        const int k = ti_cur[c];
+        col_off[c] = run;
+        ti_cur[c] = run;
+        run += k;
+    }
+    if (tid == 1023) col_off[n] = run;  // (the last thread's run ends the scan: 2 cnt)
+    __syncthreads();
+    for (unsigned int i = tid; i < cnt; i += 1024) {
+        const uint2 e = list[i];
+        const uint32_t u = e.x & 0xffffu, v = e.x >> 16;
+        col_ent[atomicAdd(&ti_cur[u], 1)] = make_uint2(v, e.y);
+        col_ent[atomicAdd(&ti_cur[v], 1)] = make_uint2(u, e.y);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // 16 lanes per row, 4 rows per wave, 1 wave per workgroup.
 #ifndef GANQ_JACOBI_SWEEPS
@@ -1180,9 +1250,21 @@ __device__ __forceinline__ uint32_t bytes_equal(uint32_t x, uint32_t pat) {  // 
     return (~t & 0x80808080u) >> 7;
 }
 
-template <int NT, int NPL>
+// steps of operands m_update_mfma_kernel keeps in flight per wave, by tiles per pass and operand planes per step.  The planes not
+// read free registers, but at 168 (three workgroups per CU) only one deeper ring fits without scratch -- two tiles, two planes, 3
+// steps -- and it measured level with 2 steps (profiles/mu_top_v1.txt): the depths are the four-plane kernel's
+constexpr int mu_depth(int nt, int npl) {
+    if (nt == 2) return npl >= 5 ? 1 : 2;
+    return npl == 6 ? 2 : npl == 5 ? 3 : 4;
+}
+
+// D dense planes of the 31-bit word (operands 0 .. D - 1 -> acc[t][0 .. D - 1]) and, with EXT, planes 4 and 5 of the extension word
+// (-> acc[t][4], acc[t][5]); the accumulators of the planes left out stay zero
+template <int NT, int D, bool EXT>
 __device__ __forceinline__ void mu_group(const int8_t* __restrict__ planes, int n, int nq, const uint8_t* __restrict__ qp,
                                          const int (&cj)[MG_TILES], int lane, int kb, int ke, v4i (&acc)[MG_TILES][6]) {
+    constexpr int NPL = D + (EXT ? 2 : 0);
+    auto pl = [](int p) { return p < D ? p : p - D + 4; };  // operand p of a step is this plane / accumulator
     const int i16 = lane & 15, kq = lane >> 4;
     const uint32_t pat = (uint32_t)i16 * 0x01010101u;
     const int64_t plane = (int64_t)n * nq;
@@ -1195,14 +1277,14 @@ __device__ __forceinline__ void mu_group(const int8_t* __restrict__ planes, int 
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int p = 0; p < NPL; ++p) bf[t][p] = *reinterpret_cast<const v4i*>(bp[t] + p * plane + k0);
+            for (int p = 0; p < NPL; ++p) bf[t][p] = *reinterpret_cast<const v4i*>(bp[t] + pl(p) * plane + k0);
     };
-    // every step is one dependent round trip to L2 / Infinity Cache: D steps of operands are kept in flight
-    // (with the extension's six planes half as many: the kernel then fits 168 registers -- three workgroups per CU instead of two for
-    // a kernel that is a chain of round trips per row; the six-plane path is the rare one)
-    constexpr int D = NPL == 6 ? (NT == 1 ? 2 : 1) : (NT == 1 ? 4 : 2);
-    uint4 cw[D];
-    v4i bf[D][NT][NPL];
+    // every step is one dependent round trip to L2 / Infinity Cache: FL steps of operands are kept in flight
+    // (with the extension's six planes half as many as with four: the kernel then fits 168 registers -- three workgroups per CU instead
+    // of two for a kernel that is a chain of round trips per row; the six-plane path is the rare one)
+    constexpr int FL = mu_depth(NT, NPL);
+    uint4 cw[FL];
+    v4i bf[FL][NT][NPL];
     auto step = [&](const uint4& c, const v4i (&b)[NT][NPL]) {
         v4i af;
         af[0] = (int)bytes_equal(c.x, pat);
@@ -1212,21 +1294,27 @@ __device__ __forceinline__ void mu_group(const int8_t* __restrict__ planes, int 
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int p = 0; p < NPL; ++p) acc[t][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, b[t][p], acc[t][p], 0, 0, 0);
+            for (int p = 0; p < NPL; ++p) acc[t][pl(p)] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, b[t][p], acc[t][pl(p)], 0, 0, 0);
     };
 #pragma unroll
-    for (int d = 0; d < D; ++d) load(min(kb + 64 * d, ke - 64), cw[d], bf[d]);
-    for (int k0 = kb; k0 < ke; k0 += 64 * D) {
+    for (int d = 0; d < FL; ++d) load(min(kb + 64 * d, ke - 64), cw[d], bf[d]);
+    for (int k0 = kb; k0 < ke; k0 += 64 * FL) {
 #pragma unroll
-        for (int d = 0; d < D; ++d) {
+        for (int d = 0; d < FL; ++d) {
             if (k0 + 64 * d < ke) step(cw[d], bf[d]);                    // uniform
-            load(min(k0 + 64 * (d + D), ke - 64), cw[d], bf[d]);        // clamped: the tail re-reads its last step
+            load(min(k0 + 64 * (d + FL), ke - 64), cw[d], bf[d]);       // clamped: the tail re-reads its last step
         }
     }
 }
 
 // With the extension word on (prep->ext, uniform) the two extra digit planes ride along in the same pass and move the
 // second set of sums Mstate_lo; the pair / diagonal corrections come from Jint / hdiag_j.
+// Of the 31-bit word only the D = mu_dense_planes(..) lowest planes are read (uniform; D = 4 wherever no exception lists exist):
+// S is linear in H, so what the planes above them hold is moved separately -- for a changed column c every listed pair (c, x) moves
+// value << 8 D into the bucket of x's OLD code, found through the per-column index of top_index_kernel; the column's own entry is
+// taken out with the low D digits of the diagonal, which is all the planes put in.  The pair corrections take the whole Hint.
+constexpr int MU_TOP_SMALL = 32;  // a column with more listed partners than this is shared out among the row's threads
+constexpr int MU_TOP_BIG = 64;    // ... as long as the row has no more than this many of them
 __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const int8_t* __restrict__ planes, const int* __restrict__ Hint,
                                                            const short* __restrict__ Jint,
                                                            const int* __restrict__ hdiag_int, const int* __restrict__ hdiag_j,
@@ -1235,12 +1323,16 @@ __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const i
                                                            const uint16_t* __restrict__ chg, const int* __restrict__ chgcnt,
                                                            long long* __restrict__ Mstate, long long* __restrict__ Mstate_lo,
                                                            const long long* __restrict__ changed, long long thr,
-                                                           const TPrep* __restrict__ prep) {
+                                                           const TPrep* __restrict__ prep, const int* __restrict__ col_off,
+                                                           const uint2* __restrict__ col_ent, int mu_top) {
     if (*changed > thr) return;  // the full accumulation runs instead
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int cnt = chgcnt[row];
     if (cnt == 0) return;
     const bool ext = prep->ext != 0;
+    // (uniform) the D the index of this H was built for; without one -- t_prepare ran under GANQ_MU_TOP=0 -- all four planes
+    const int D = (mu_top == 0 || prep->mu_index == 0) ? 4 : prep->mu_index;
+    const bool listed = D < 4 && (D == 2 ? prep->c2 : prep->c3) != 0;                         // entries above the dense planes exist
     __shared__ long long Frow[256];
     __shared__ long long Flo[256];
     long long* Fg = Mstate + (int64_t)row * 256;
@@ -1254,11 +1346,20 @@ __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const i
     constexpr int CAP = 512;
     __shared__ uint16_t s_col[CAP];
     __shared__ uint8_t s_old[CAP], s_new[CAP];
+    __shared__ int s_tb[CAP];        // the column's run of the per-column index: begin, length (read here, beside the codes: the
+    __shared__ uint16_t s_tl[CAP];   // list phase below then starts without a round trip of its own)
+    __shared__ int s_big[MU_TOP_BIG], s_nbig;
+    if (tid == 0) s_nbig = 0;
     for (int e = tid; e < min(cnt, CAP); e += MG_WAVES * 64) {
         const int c = list[e];
         s_col[e] = (uint16_t)c;
         s_old[e] = (uint8_t)min((int)qp[c], 15);
         s_new[e] = (uint8_t)min((int)qn[c], 15);
+        if (listed) {
+            const int b0 = col_off[c];
+            s_tb[e] = b0;
+            s_tl[e] = (uint16_t)(col_off[c + 1] - b0);  // (a column has fewer than n <= 32768 partners)
+        }
     }
     __syncthreads();
     auto col_of = [&](int e) -> int { return e < CAP ? (int)s_col[e] : (int)list[e]; };
@@ -1289,12 +1390,20 @@ __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const i
         for (int t = 0; t < MG_TILES; ++t)
 #pragma unroll
             for (int p = 0; p < 6; ++p) acc[t][p] = v4i{0, 0, 0, 0};
+        auto group = [&](auto d_tag, auto ext_tag) {
+            constexpr int DD = decltype(d_tag)::value;
+            constexpr bool EE = decltype(ext_tag)::value;
+            if (nt == 1) mu_group<1, DD, EE>(planes, n, nq, qp, cj, lane, kb, ke, acc);
+            else mu_group<2, DD, EE>(planes, n, nq, qp, cj, lane, kb, ke, acc);
+        };
         if (ext) {
-            if (nt == 1) mu_group<1, 6>(planes, n, nq, qp, cj, lane, kb, ke, acc);
-            else mu_group<2, 6>(planes, n, nq, qp, cj, lane, kb, ke, acc);
+            if (D == 2) group(std::integral_constant<int, 2>{}, std::true_type{});
+            else if (D == 3) group(std::integral_constant<int, 3>{}, std::true_type{});
+            else group(std::integral_constant<int, 4>{}, std::true_type{});
         } else {
-            if (nt == 1) mu_group<1, 4>(planes, n, nq, qp, cj, lane, kb, ke, acc);
-            else mu_group<2, 4>(planes, n, nq, qp, cj, lane, kb, ke, acc);
+            if (D == 2) group(std::integral_constant<int, 2>{}, std::false_type{});
+            else if (D == 3) group(std::integral_constant<int, 3>{}, std::false_type{});
+            else group(std::integral_constant<int, 4>{}, std::false_type{});
         }
         // D layout: lane (j = lane & 15, kq) holds S[b = 4 kq + r][change j], r = 0..3
 #pragma unroll
@@ -1302,7 +1411,8 @@ __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const i
             const int e = g0 + 16 * t + i16;
             if (t < nt && e < cnt) {
                 const int a_old = old_of(e), a_new = new_of(e);
-                const long long self = wv == 0 ? (long long)hdiag_int[cj[t]] : 0;
+                // (what the D planes hold of the column's own entry; the planes left out have zero accumulators: the sum below is theirs)
+                const long long self = wv == 0 ? low_digits((long long)hdiag_int[cj[t]], D) : 0;
                 const long long self_lo = (ext && wv == 0) ? (long long)hdiag_j[cj[t]] : 0;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1318,6 +1428,46 @@ __global__ __launch_bounds__(MG_WAVES * 64, 3) void m_update_mfma_kernel(const i
                     }
                 }
             }
+        }
+    }
+    // the listed entries of the changed columns: what the digits above the D dense planes hold, with the OLD code of the partner
+    if (listed) {
+        const int sh = 8 * D;
+        auto entry = [&](int a_old, int a_new, const uint2 en) {
+            const uint32_t b = qp[en.x];
+            if (b < 16u) move(a_old, a_new, (int)b, (long long)(int)en.y * (1ll << sh));  // (the matrix sum, too, has no bucket for codes >= 16)
+        };
+        for (int e = tid; e < cnt; e += MG_WAVES * 64) {
+            int b0, len;
+            if (e < CAP) {
+                b0 = s_tb[e];
+                len = s_tl[e];
+            } else {
+                const int c = list[e];
+                b0 = col_off[c];
+                len = col_off[c + 1] - b0;
+            }
+            if (len == 0) continue;
+            // a massive column itself: left to the whole workgroup, if the table has room.  (A row that changes more than MU_TOP_BIG
+            // such columns at once walks the others' runs in one thread each, up to n entries in a row: correct, slow, and only met
+            // with a long list and hundreds of changes in one row.)
+            if (len > MU_TOP_SMALL) {
+                const int slot = atomicAdd(&s_nbig, 1);
+                if (slot < MU_TOP_BIG) {
+                    s_big[slot] = e;
+                    continue;
+                }
+            }
+            const int a_old = old_of(e), a_new = new_of(e);
+            for (int i = 0; i < len; ++i) entry(a_old, a_new, col_ent[b0 + i]);
+        }
+        __syncthreads();
+        const int nbig = min(s_nbig, MU_TOP_BIG);
+        for (int k = 0; k < nbig; ++k) {
+            const int e = s_big[k], c = col_of(e);
+            const int b0 = col_off[c], len = col_off[c + 1] - b0;
+            const int a_old = old_of(e), a_new = new_of(e);
+            for (int i = tid; i < len; i += MG_WAVES * 64) entry(a_old, a_new, col_ent[b0 + i]);
         }
     }
     // earlier changes e' < e of the row already carry their new code when change e is applied: all pairs at once
@@ -1809,6 +1959,7 @@ TLayout t_layout(int64_t m, int64_t n, bool with_f64) {
     lo.off_hint = lo.off_qprev = lo.off_mstate = lo.off_chg = lo.off_chgcnt = 0;
     lo.off_wp = lo.off_hp = lo.off_rexp = lo.off_wlo = 0;
     lo.off_active = 0;
+    lo.off_topoff = lo.off_topent = 0;
     if (with_f64) {
         lo.off_hint = take((size_t)n * n * sizeof(int));
         lo.off_qprev = take((size_t)m * n);
@@ -1820,6 +1971,8 @@ TLayout t_layout(int64_t m, int64_t n, bool with_f64) {
         lo.off_chg = take((size_t)m * n * sizeof(uint16_t));
         lo.off_chgcnt = take((size_t)m * sizeof(int) + 64);  // counts per row, then the 8-byte total
         lo.off_active = take(((size_t)m + 1) * sizeof(int));  // rows that changed in the last iteration, their number
+        lo.off_topoff = take(((size_t)n + 1) * sizeof(int));
+        lo.off_topent = take((size_t)2 * TOP_LIST_MAX * sizeof(uint2));
         if (wh_use_f64_gemm()) {
             lo.off_h64 = take((size_t)n * n * sizeof(double));
         } else {
@@ -1894,6 +2047,16 @@ int t_prepare(const float* W, const float* H, int64_t m, int64_t n, const TLayou
                        planes, hdiag, hdiag_j, H64, Hint, Jint, reinterpret_cast<uint2*>(ws + lo.off_top3),
                        reinterpret_cast<uint2*>(ws + lo.off_top2), per_wg);
     GANQ_LAUNCH_CHECK();
+    // (not under GANQ_MU_TOP=0: the incremental sums then read all four planes and need no index; TPrep::mu_index stays zero)
+    if (with_f64 && lo.off_topent && top_cap_in_force(m, n) >= 0 && opt_get(OPT_MU_TOP) != 0) {
+        const size_t ilds = (size_t)n * sizeof(int);
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(top_index_kernel), ilds);
+        if (rc) return rc;
+        hipLaunchKernelGGL(top_index_kernel, dim3(1), dim3(1024), ilds, stream, reinterpret_cast<const uint2*>(ws + lo.off_top3),
+                           reinterpret_cast<const uint2*>(ws + lo.off_top2), prep, (int)n, reinterpret_cast<int*>(ws + lo.off_topoff),
+                           reinterpret_cast<uint2*>(ws + lo.off_topent), (int)opt_get(OPT_MU_TOP));
+        GANQ_LAUNCH_CHECK();
+    }
     if (with_f64) {
         // change counter of the incremental bucket sums: zero once, every t_solve leaves it zero again
         GANQ_HIP_CHECK(hipMemsetAsync(ws + lo.off_chgcnt + align_up((size_t)m * sizeof(int), 8), 0, sizeof(long long), stream));
@@ -1956,7 +2119,9 @@ int t_iterate(const uint8_t* Q, int64_t m, int64_t n, int V, double rcond, const
         const short* Jint = reinterpret_cast<const short*>(ws + lo.off_jint);
         if ((n & 15) == 0 && !mu_lds)
             hipLaunchKernelGGL(m_update_mfma_kernel, dim3((unsigned)m), dim3(MG_WAVES * 64), 0, stream, planes, Hint, Jint, hdiag,
-                               hdiag_j, Q, qprev, (int)m, (int)n, (int)lo.nq, chg, chgcnt, mstate, mstate_lo, changed, gated ? thr : LLONG_MAX, prep);
+                               hdiag_j, Q, qprev, (int)m, (int)n, (int)lo.nq, chg, chgcnt, mstate, mstate_lo, changed, gated ? thr : LLONG_MAX, prep,
+                               reinterpret_cast<const int*>(ws + lo.off_topoff), reinterpret_cast<const uint2*>(ws + lo.off_topent),
+                               (int)opt_get(OPT_MU_TOP));
         else {
             int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(m_update_kernel<int>), usmem);
             if (!rc) rc = ensure_dynamic_lds(reinterpret_cast<const void*>(m_update_kernel<short>), usmem);
@@ -2093,6 +2258,17 @@ extern "C" int ganq_debug_top_rule(int64_t m, int64_t n, long long c3, long long
     out[0] = top_dense_planes(c3, c2, cap);
     out[1] = cap;
     out[2] = TOP_LIST_MAX;
+    return 0;
+}
+
+// tests: how many digit planes the incremental bucket sums on the matrix cores read for an [m, n] layer whose H has c3 / c2 exceptions,
+// under the current options (host only: mu_dense_planes is the function the kernel evaluates).  out: its D, the full sum's D
+extern "C" int ganq_debug_mu_planes(int64_t m, int64_t n, long long c3, long long c2, int* out) {
+    if (!out) return fail(-3, "ganq_debug_mu_planes: null pointer");
+    if (m <= 0 || n <= 0 || c3 < 0 || c2 < c3) return fail(-1, "ganq_debug_mu_planes: bad shape / counts");
+    const int cap = top_cap_in_force(m, n);
+    out[0] = mu_dense_planes(c3, c2, cap, (int)opt_get(OPT_MU_TOP));
+    out[1] = top_dense_planes(c3, c2, cap);
     return 0;
 }
 

@@ -177,6 +177,11 @@ int ganq_debug_top_rule(int64_t m, int64_t n, long long c3, long long c2, int* o
 /* ... and on the device: the quantisation of the preparation for H [n,n] (device) of an [m, n] layer.
  * out[5] (host) = { c3, c2, cap in force, capacity of a list, D }. */
 int ganq_debug_top_planes(const float* H, int64_t n, int64_t m, long long* out, void* stream);
+/* The incremental bucket sums on the matrix cores (m_update_mfma_kernel) read the same D digit planes and take the entries above them
+ * from a per-column index of the list in force.  GANQ_MU_TOP: -1 as described, 0 always all four planes, 3 (A/B) as described
+ * but never fewer than three planes (with D = 2 in the full sum the entries above digit 2 come from the other list).  The rule alone, host only,
+ * from the function the kernel evaluates: out[2] = { D of the incremental kernel, D of the full sum }. */
+int ganq_debug_mu_planes(int64_t m, int64_t n, long long c3, long long c2, int* out);
 
 /* ---- dense fp32 product C[m,n] = A[m,k] @ B[k,n] on the fp32 matrix cores (W@H, ganq.py:590) */
 int ganq_matmul_f32(const float* A, const float* B, int64_t m, int64_t k, int64_t n, float* C, void* stream);

@@ -105,6 +105,8 @@ SIGNATURES = {
     "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "ganq_lut_table_assign": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp]),
+    "ganq_lut_table_lookup": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_outlier_cutoffs": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_extract": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_matmul": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -704,6 +706,45 @@ def lut_embedding(ids, qweight, lut, in_features: int, bits: int, outliers=None,
     _call("ganq_lut_embedding", (ids, qweight, lut, rowptr, cols, vals, out), ids.data_ptr(), N, qweight.data_ptr(), lut.data_ptr(), code, m, n,
           bits, _ptr(rowptr), _ptr(cols) if cols is not None and cols.numel() else None,
           _ptr(vals) if vals is not None and vals.numel() else None, out.data_ptr(), _ST)
+    return out
+
+
+def lut_table_assign(W, T, bits: int, want_sqerr: bool = True):
+    """nearest-code assignment of a table's rows into the row-packed layout: W [m,n] fp32, T [m, 2^bits] fp32 ->
+    (qrows int32 [m, n*bits/32] == pack_indices(Q, bits).t(), sqerr fp64 [m] or None); ties go to the lower index"""
+    W, T = _dev_f32(W, "W"), _dev_f32(T, "T")
+    m, n = W.shape
+    if tuple(T.shape) != (m, 2 ** bits):
+        raise GanqHipError(f"lut_table_assign: T {tuple(T.shape)} does not fit W {tuple(W.shape)} at {bits} bits")
+    qrows = torch.empty((m, n * bits // 32), dtype=torch.int32, device=W.device)
+    sqerr = torch.empty((m,), dtype=torch.float64, device=W.device) if want_sqerr else None
+    _call("ganq_lut_table_assign", (W, T, qrows, sqerr), W.data_ptr(), T.data_ptr(), m, n, int(bits), qrows.data_ptr(), _ptr(sqerr), _ST)
+    return qrows, sqerr
+
+
+def lut_table_lookup(ids, qrows, lut, bits: int, out=None):
+    """rows of a row-packed LUT table by id: ids int64 (any shape), qrows int32 [m, n*bits/32], lut [m, 2^bits] fp16 / bf16 ->
+    [..., n] in lut's dtype.  An id outside [0, m) gives a row of zeros.  One launch, nothing else: capturable in a HIP graph
+    (pass `out` to keep the address fixed)."""
+    code = _act_dtype(lut, "lut")
+    if ids.dtype != torch.int64 or not ids.is_cuda:
+        raise GanqHipError("lut_table_lookup: ids must be an int64 cuda tensor")
+    if qrows.dtype != torch.int32 or qrows.dim() != 2 or not qrows.is_cuda:
+        raise GanqHipError("lut_table_lookup: qrows must be a 2-d int32 cuda tensor")
+    ids, qrows, lut = ids.contiguous(), qrows.contiguous(), lut.contiguous()
+    m = lut.shape[0]
+    n = qrows.shape[1] * 32 // bits
+    if qrows.shape[0] != m or n * bits != qrows.shape[1] * 32 or lut.shape[1] != 2 ** bits:
+        raise GanqHipError(f"lut_table_lookup: qrows {tuple(qrows.shape)} / lut {tuple(lut.shape)} do not fit one table at {bits} bits")
+    N = ids.numel()
+    if out is None:
+        out = torch.empty(tuple(ids.shape) + (n,), dtype=lut.dtype, device=lut.device)
+    elif out.dtype != lut.dtype or out.numel() != N * n or not out.is_contiguous() or not out.is_cuda:
+        raise GanqHipError("lut_table_lookup: out must be a contiguous cuda tensor of lut's dtype with ids.numel() * embedding_dim elements")
+    if m == 0:  # (the library leaves `out` alone for an empty table; every id is out of range: rows of zeros)
+        return out.zero_()
+    _call("ganq_lut_table_lookup", (ids, qrows, lut, out), ids.data_ptr(), N, qrows.data_ptr(), lut.data_ptr(), code, m, n, int(bits),
+          out.data_ptr(), _ST)
     return out
 
 

@@ -36,6 +36,7 @@ class GPTQProcessor:
         self._results: Dict[str, Dict[str, torch.Tensor]] = {}
         self.log = []  # one row per module, like the reference's quant_log (writer.py:54-60)
         self.unquantized = []  # modules that saw no calibration data (MoE experts) and were left as they are
+        self.embedding_stage_seconds = None  # set by quantize_model when `ganq_embedding` quantizes the input embedding
 
     def preprocess(self, module: NamedModule, buffered_fwd: bool = False):
         if self.qcfg.dynamic_get(layer_name=module.full_name) is False:  # '-:' pattern: module skipped

@@ -12,6 +12,9 @@ save/load       the packed format the reference lacks: it can only save FORMAT.F
                    With `QuantizeConfig.lm_head` the output head is one more entry of `"modules"`; an input embedding served from the
                    packed head (`ganq_tied_embedding="share"`) has no tensor in the file and is recorded as
                    `"tied_embedding": {"module": <embedding>, "source": <head>}` (absent in older checkpoints: nothing shared).
+                   An input embedding quantized on its own (`QuantizeConfig.ganq_embedding`) is `<name>.qweight_rows` int32
+                   [vocab, dim*bits/32] / `<name>.lut` fp16 [vocab, 2^bits] and an entry of `"embeddings"`: {<name>: {"bits",
+                   "num_embeddings", "embedding_dim", "padding_idx"}} (absent in older checkpoints: no packed embedding).
 gptq_style_ppl  the evaluator behind the README numbers (examples/quantization/basic_usage_wikitext2.py:63-93):
                    non-overlapping windows of `seqlen` tokens, mean token NLL, exp.
 """
@@ -27,8 +30,10 @@ from ..looper.gptq_processor import GPTQProcessor
 from ..looper.module_looper import ModuleLooper
 from ..looper.named_module import NamedModule
 from ..adapter import Lora
-from ..nn_modules.qlinear.ganq_hip import GanqHipQuantEmbedding, GanqHipQuantLinear
+from .. import _lib
+from ..nn_modules.qlinear.ganq_hip import GanqHipPackedEmbedding, GanqHipQuantEmbedding, GanqHipQuantLinear
 from ..quantization.config import FORMAT, QuantizeConfig
+from ..quantization.embedding import check_embedding_shape, quantize_embedding_rows
 from .definitions import LayerMap, layer_map_for
 
 
@@ -125,6 +130,72 @@ class _Head:
                                                                           padding_idx=self.embedding.padding_idx))
 
 
+class _Embedding:
+    """the input embedding as the embedding stage of quantize_model needs it (`QuantizeConfig.ganq_embedding`): every refusal
+    happens here, before any work"""
+
+    def __init__(self, model: nn.Module, qcfg: QuantizeConfig):
+        get = getattr(model, "get_input_embeddings", None)
+        self.module = get() if get is not None else None
+        if self.module is None:
+            raise ValueError("QuantizeConfig.ganq_embedding: the model has no input embeddings (get_input_embeddings())")
+        self.name = _name_of(model, self.module)
+        self.skipped = qcfg.dynamic_get(layer_name=self.name) is False  # '-:' pattern
+        if self.skipped:
+            return
+        if type(self.module) is not nn.Embedding:
+            raise NotImplementedError(f"QuantizeConfig.ganq_embedding: the input embedding is a {type(self.module).__name__}; only a "
+                                      f"plain nn.Embedding is a row lookup of its table")
+        if self.module.max_norm is not None:
+            raise NotImplementedError("QuantizeConfig.ganq_embedding: an nn.Embedding with max_norm renormalises its rows on every "
+                                      "lookup; a packed table cannot")
+        w = self.module.weight
+        served = (torch.float16, torch.bfloat16) + ((torch.float32,) if qcfg.format == FORMAT.FAKE else ())
+        if w.dtype not in served:
+            raise NotImplementedError(f"QuantizeConfig.ganq_embedding: a {w.dtype} table cannot be packed for format `{qcfg.format}` "
+                                      f"({', '.join(str(d) for d in served)} can)")
+        self.bits = int(qcfg.dynamic_get(self.name, "bits", qcfg.bits))
+        check_embedding_shape(self.module.embedding_dim, self.bits)
+        get = getattr(model, "get_output_embeddings", None)
+        head = get() if get is not None else None
+        hw = getattr(head, "weight", None)
+        self.tied = isinstance(hw, torch.Tensor) and (hw is w or hw.data_ptr() == w.data_ptr())
+
+    def quantize(self, model: nn.Module, qcfg: QuantizeConfig, proc: GPTQProcessor) -> None:
+        """quantize the table (quantization/embedding.py) and put the result where the calibration passes will read it.  A tie is
+        broken first: the head keeps the original Parameter, the embedding is quantized from its values."""
+        emb = self.module
+        w = emb.weight
+        dev = w.device
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        t0 = time.time()
+        qrows, T, sqerr = quantize_embedding_rows(w.detach(), self.bits)
+        lut = T.to(torch.float16)
+        if self.tied:
+            cfg = getattr(model, "config", None)
+            if cfg is not None and getattr(cfg, "tie_word_embeddings", False):
+                cfg.tie_word_embeddings = False  # tie_weights() must not hand the head's table back to the embedding
+        if qcfg.format == FORMAT.GANQ_LUT:
+            packed = GanqHipPackedEmbedding(emb.num_embeddings, emb.embedding_dim, self.bits, dtype=w.dtype, padding_idx=emb.padding_idx)
+            packed.qweight_rows, packed.lut = qrows, lut
+            packed.train(emb.training)
+            _set_module(model, self.name, packed)
+        else:  # FORMAT.FAKE: the rows the packed module would return, in the table's dtype
+            served = w.dtype if w.dtype in (torch.float16, torch.bfloat16) else torch.float16
+            deq = _lib.lut_table_lookup(torch.arange(emb.num_embeddings, device=dev), qrows, lut.to(served), self.bits).to(w.dtype)
+            if self.tied:
+                emb.weight = nn.Parameter(deq, requires_grad=w.requires_grad)
+            else:
+                w.data = deq
+        total = float(sqerr.sum())
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        proc.embedding_stage_seconds = time.time() - t0
+        proc.log.append({"layer": -1, "module": self.name, "bits": self.bits, "loss": f"{total:.5f}",
+                         "time": f"{proc.embedding_stage_seconds:.3f}"})
+
+
 def _quantize_head(proc: GPTQProcessor, model: nn.Module, lm: LayerMap, head: _Head, hidden, layer_index: int, progress=None):
     """the head as one one-module group of the same processor, under its real module name, on `pre_head` of the hidden states
     leaving the last decoder layer (the looper's outputs: what the quantized body feeds it)"""
@@ -153,9 +224,10 @@ def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: 
                    **looper_options) -> GPTQProcessor:
     """Quantize every Linear the layer map names, layer by layer, on the device the model lives on (with `qcfg.lm_head` also the
     output head, last, on the normalised hidden states the quantized body produces; a tied input embedding follows
-    `qcfg.ganq_tied_embedding`).  `calibration`:
+    `qcfg.ganq_tied_embedding`; with `qcfg.ganq_embedding` the input embedding itself, FIRST, so that every calibration pass runs
+    through the quantized embedding).  `calibration`:
     token-id tensors [b, seq].  Returns the processor (per-module log, results); the model is modified in place
-    (GanqHipQuantLinear modules for FORMAT.GANQ_LUT, dequantised nn.Linear weights for FORMAT.FAKE).
+    (GanqHipQuantLinear / GanqHipPackedEmbedding modules for FORMAT.GANQ_LUT, dequantised weights for FORMAT.FAKE).
     looper_options: `early_exit=` / `cache_outputs=` / `share_group_hessian=` of ModuleLooper (results do not depend on
     them).  processor: a GPTQProcessor (subclass) to drive instead of a fresh one -- the reference's LoopProcessor slot."""
     lm = layer_map or layer_map_for(model)
@@ -178,11 +250,26 @@ def quantize_model(model: nn.Module, calibration: Sequence[torch.Tensor], qcfg: 
         head = _Head(model, qcfg)
         if head.skipped:
             head = None
+    embedding = None
+    if qcfg.ganq_embedding:
+        if dist.world > 1:
+            raise NotImplementedError("QuantizeConfig.ganq_embedding with several ranks: every rank would quantize the whole table; "
+                                      "quantize on one GPU")
+        embedding = _Embedding(model, qcfg)
+        if embedding.skipped:
+            embedding = None
+        elif head is not None and head.share:
+            raise ValueError("QuantizeConfig: ganq_embedding=True with lm_head=True and ganq_tied_embedding=`share`: `share` already "
+                             "serves the embedding from the head's packed table (use `untie` to pack both)")
     batches = [b.to(dev) for b in (calibration[dist.rank::dist.world] if local else calibration)]
     was_training = model.training
     model.eval()
-    hidden, kwargs_list = capture_layer_inputs(model, layers, batches)
     proc = processor if processor is not None else GPTQProcessor(qcfg)
+    if embedding is not None:
+        embedding.quantize(model, qcfg, proc)
+        if head is not None and embedding.tied:
+            head = _Head(model, qcfg)  # the tie is gone: the head stage finds a head of its own
+    hidden, kwargs_list = capture_layer_inputs(model, layers, batches)
     looper_options.setdefault("share_group_hessian", lm.shared_group_inputs)
 
     def fwd(layer, x, kw):
@@ -221,7 +308,9 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
                for n, m in model.named_modules() if isinstance(m, GanqHipQuantLinear)}
     # the codebook is stored as fp16 also while it trains as an fp32 parameter (train_codebook): the format does not change
     # (likewise the adapter while it trains, train_adapter)
-    luts = {f"{n}.{k}" for n in modules for k in ("lut", "lora_A", "lora_B")}
+    embeddings = {n: {"bits": m.bits, "num_embeddings": m.num_embeddings, "embedding_dim": m.embedding_dim, "padding_idx": m.padding_idx}
+                  for n, m in model.named_modules() if isinstance(m, GanqHipPackedEmbedding)}
+    luts = {f"{n}.{k}" for n in modules for k in ("lut", "lora_A", "lora_B")} | {f"{n}.lut" for n in embeddings}
     state = {k: (v.detach().to(torch.float16) if k in luts else v.detach()).contiguous().cpu() for k, v in model.state_dict().items()}
     # tied weights (lm_head <-> embeddings) share storage: safetensors wants each tensor once
     seen, out = {}, {}
@@ -234,6 +323,8 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
     save_file(out, os.path.join(path, "model.safetensors"), metadata={"format": "pt", "ganq_format": FORMAT.GANQ_LUT})
     cfg = qcfg.to_dict()
     cfg["modules"] = modules
+    if embeddings:
+        cfg["embeddings"] = embeddings
     for n, m in model.named_modules():  # an embedding served from the packed head: the checkpoint holds no table for it
         if isinstance(m, GanqHipQuantEmbedding):
             cfg["tied_embedding"] = {"module": n, "source": _name_of(model, m.head)}
@@ -244,13 +335,15 @@ def save_quantized(model: nn.Module, path: str, qcfg: Optional[QuantizeConfig] =
 def load_quantized(model: nn.Module, path: str) -> nn.Module:
     """`model`: a freshly constructed (unquantized, any weights) instance of the same architecture.  Replaces the
     recorded Linear modules by GanqHipQuantLinear (the output head among them if it was quantized; an embedding recorded as
-    `"tied_embedding"` by a GanqHipQuantEmbedding on the rebuilt head), then loads every tensor of the checkpoint."""
+    `"tied_embedding"` by a GanqHipQuantEmbedding on the rebuilt head; one recorded under `"embeddings"` by a
+    GanqHipPackedEmbedding), then loads every tensor of the checkpoint."""
     from safetensors.torch import load_file
 
     with open(os.path.join(path, "quantize_config.json")) as f:
         cfg = json.load(f)
     modules: Dict[str, dict] = cfg.pop("modules")
     tied = cfg.pop("tied_embedding", None)
+    embeddings: Dict[str, dict] = cfg.pop("embeddings", None) or {}
     qcfg = QuantizeConfig.from_dict(cfg)
     named = dict(model.named_modules())
     get_head = getattr(model, "get_output_embeddings", None)
@@ -269,8 +362,13 @@ def load_quantized(model: nn.Module, path: str) -> nn.Module:
         emb = named[tied["module"]]
         _set_module(model, tied["module"], GanqHipQuantEmbedding(_get_module(model, tied["source"]), dtype=table_dtype,
                                                                  padding_idx=getattr(emb, "padding_idx", None)))
-    if head_packed and getattr(getattr(model, "config", None), "tie_word_embeddings", False):
-        model.config.tie_word_embeddings = False  # a packed head has no `weight`: tie_weights() below must not re-tie it
+    for name, info in embeddings.items():  # built before load_state_dict: the checkpoint's tensors find their buffers
+        emb = named[name]
+        _set_module(model, name, GanqHipPackedEmbedding(info["num_embeddings"], info["embedding_dim"], info["bits"], dtype=emb.weight.dtype,
+                                                        padding_idx=info.get("padding_idx")).to(emb.weight.device))
+    if (head_packed or embeddings) and getattr(getattr(model, "config", None), "tie_word_embeddings", False):
+        # a packed head / a packed embedding has no `weight`: tie_weights() below must not reach for it
+        model.config.tie_word_embeddings = False
     state = load_file(os.path.join(path, "model.safetensors"))
     missing, unexpected = model.load_state_dict(state, strict=False)
     missing = [k for k in missing if k not in ("lm_head.weight",)]  # tied to the embeddings

@@ -373,4 +373,54 @@ class GanqHipQuantEmbedding(nn.Module):
         return f"{self.num_embeddings}, {self.embedding_dim}, bits={self._head.bits}, dtype={self.dtype}"
 
 
-__all__ = ["GanqHipQuantLinear", "GanqHipQuantEmbedding", "BACKEND_GANQ_HIP"]
+class GanqHipPackedEmbedding(nn.Module):
+    """An input embedding quantized on its own (`QuantizeConfig.ganq_embedding`): it owns
+      qweight_rows  int32 [num_embeddings, embedding_dim * bits / 32]   the row-packed indices: row `id` is the bit stream column `id`
+                                                                        of a GanqHipQuantLinear's `qweight` would hold, so a
+                                                                        token's row is embedding_dim * bits / 8 contiguous bytes
+      lut           fp16  [num_embeddings, 2^bits]                      per-row codebook
+    and `forward(ids)` is `lut[id][Q[id][:]]`, one HIP launch (csrc/lut_table.hip).  Ids of any shape give `[..., embedding_dim]` in
+    `dtype` (the dtype of the table this module replaced: fp16 or bf16; the codebook is converted once and kept); an id outside the
+    vocabulary gives a row of zeros.  `padding_idx` is kept for the record and not read (nn.Embedding's forward does not read it
+    either: it only masks the gradient).
+
+    No gradient flows through it, it has no adapter (an adapter corrects a layer's output under its inputs; a lookup has none) and
+    no outliers: the outlier split of `ganq_outlier_ratio` is not applied to embeddings."""
+
+    SUPPORTS_BITS = [2, 3, 4]
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, dtype: torch.dtype = torch.float16, padding_idx=None):
+        super().__init__()
+        if bits not in self.SUPPORTS_BITS:
+            raise NotImplementedError(f"GanqHipPackedEmbedding: bits={bits} not supported ({self.SUPPORTS_BITS} are)")
+        if embedding_dim % 32 != 0:
+            raise NotImplementedError(f"GanqHipPackedEmbedding: embedding_dim={embedding_dim} must be a multiple of 32")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"GanqHipPackedEmbedding: a table of {dtype} cannot be served (float16 and bfloat16 can)")
+        self.num_embeddings, self.embedding_dim, self.bits = int(num_embeddings), int(embedding_dim), int(bits)
+        self.dtype = dtype
+        self.padding_idx = padding_idx
+        self.register_buffer("qweight_rows", torch.zeros((self.num_embeddings, self.embedding_dim * self.bits // 32), dtype=torch.int32))
+        self.register_buffer("lut", torch.zeros((self.num_embeddings, 2 ** self.bits), dtype=torch.float16))
+
+    _as_dtype = GanqHipQuantEmbedding._as_dtype
+
+    @torch.no_grad()
+    def forward(self, ids: torch.Tensor):
+        if not ids.is_cuda:
+            raise _lib.GanqHipError("GanqHipPackedEmbedding runs on the GPU only (no CPU fallback)")
+        if ids.dtype != torch.int64:
+            if ids.is_floating_point() or ids.dtype == torch.bool:
+                raise TypeError(f"GanqHipPackedEmbedding: ids must be integers, got {ids.dtype}")
+            ids = ids.long()
+        return _lib.lut_table_lookup(ids, self.qweight_rows, self._as_dtype("_lut_cache", self.lut), self.bits)
+
+    def dequantize_weight(self) -> torch.Tensor:
+        """the table [num_embeddings, embedding_dim] in `dtype`: a lookup of every id"""
+        return self.forward(torch.arange(self.num_embeddings, device=self.qweight_rows.device))
+
+    def extra_repr(self) -> str:
+        return f"{self.num_embeddings}, {self.embedding_dim}, bits={self.bits}, dtype={self.dtype}"
+
+
+__all__ = ["GanqHipQuantLinear", "GanqHipQuantEmbedding", "GanqHipPackedEmbedding", "BACKEND_GANQ_HIP"]

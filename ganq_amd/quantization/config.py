@@ -90,6 +90,12 @@ class QuantizeConfig:
     # (GanqHipQuantEmbedding; no second table in memory or in the checkpoint -- the body was calibrated on the exact embedding,
     # so it never saw the embedding's quantization error).  Without a tie the field has no effect.
     ganq_tied_embedding: str = field(default="untie", metadata={"choices": ["untie", "share"]})
+    # not in the reference: quantize the INPUT embedding on its own, first, into a row-packed LUT table (GanqHipPackedEmbedding;
+    # quantization/embedding.py).  A lookup has no activations, so its rows need no Hessian: the optimal 1-D k-means of each row is
+    # the optimum.  Bits: `bits`, or a `dynamic` override under the embedding's module name; a '-:' pattern leaves it alone.  Every
+    # calibration pass then runs through the quantized embedding.  A tie to the head is broken first (the head keeps the original
+    # table); together with lm_head=True and ganq_tied_embedding="share" it is refused -- "share" already serves the embedding.
+    ganq_embedding: bool = field(default=False)
 
     def __post_init__(self):
         info = fields(self)

@@ -333,6 +333,22 @@ int ganq_lut_embedding(const int64_t* ids, int64_t N, const int32_t* qweight, co
                        int bits, const int32_t* outlier_rowptr, const int32_t* outlier_cols, const void* outlier_vals, void* out,
                        void* stream);
 
+/* a LUT-quantized table whose ROWS are looked up (an input embedding quantized on its own), in a row-packed layout:
+ *   qrows [m, n * bits / 32] int32, row-major; row `id` holds the little-endian bit stream column `id` of the GPTQ layout holds
+ *   (32 indices in `bits` words), so qrows == transpose(qweight): a token's row is n * bits / 8 contiguous bytes.
+ *   n a multiple of 32, bits 2, 3 or 4.  m == 0 (and N == 0) is a no-op.
+ * ganq_lut_table_assign: W [m,n] fp32 (16-byte aligned), T [m, 2^bits] fp32 -> qrows, Q[o][j] = the FIRST v that minimises
+ *   fabsf(W[o][j] - T[o][v]) (fp32 subtraction, v scanned upwards with a strict <), written straight into the packed words;
+ *   sqerr_rows [m] fp64 (or NULL) = sum_j (double)d * d of the fp32 differences d to the chosen codes, summed in a fixed order
+ *   (no atomics: bitwise repeatable).
+ * ganq_lut_table_lookup: out [N, n] (dtype 0 = fp16, 1 = bf16; 16-byte aligned) row t = lut[id][Q[id][:]], id = ids[t]; an id outside
+ *   [0, m) gives a row of zeros and reads nothing.  lut [m, 2^bits] in dtype.  No workspace, no host synchronisation, no allocation:
+ *   one launch, capturable in a HIP graph. */
+int ganq_lut_table_assign(const float* W, const float* T, int64_t m, int64_t n, int bits, int32_t* qrows, double* sqerr_rows,
+                          void* stream);
+int ganq_lut_table_lookup(const int64_t* ids, int64_t N, const int32_t* qrows, const void* lut, int dtype, int64_t m, int64_t n,
+                          int bits, void* out, void* stream);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,

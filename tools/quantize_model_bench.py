@@ -27,7 +27,7 @@ ARCHS = {
 
 
 def run(arch="opt-125m", nsamples=128, seqlen=2048, batch=8, bits=4, iters=10, layers=0, looper_options=None, lm_head=False,
-        tied_embedding="untie"):
+        tied_embedding="untie", embedding=False):
     import transformers
 
     from ganq_amd.models import gptq_style_ppl, quantize_model
@@ -44,7 +44,8 @@ def run(arch="opt-125m", nsamples=128, seqlen=2048, batch=8, bits=4, iters=10, l
     test_ids = torch.randint(0, cfg.vocab_size, (1, seqlen * 4), generator=g)
     ppl_fp = gptq_style_ppl(model, test_ids, seqlen)
     qcfg = QuantizeConfig(bits=bits, act_sort="asc", l_damp_style="ganq", dead="mean", ganq_iterations=iters,
-                          damp_percent=0.01, desc_act=True, lm_head=lm_head, ganq_tied_embedding=tied_embedding)
+                          damp_percent=0.01, desc_act=True, lm_head=lm_head, ganq_tied_embedding=tied_embedding,
+                          ganq_embedding=embedding)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     proc = quantize_model(model, calib, qcfg, **(looper_options or {}))
@@ -64,6 +65,9 @@ def run(arch="opt-125m", nsamples=128, seqlen=2048, batch=8, bits=4, iters=10, l
     if lm_head:  # the head stage: pre_head + Hessian of every calibration token + the head's quantize()
         head = {"lm_head": True, "ganq_tied_embedding": tied_embedding, "head_stage_s": round(proc.head_stage_seconds, 3),
                 "embedding": type(model.get_input_embeddings()).__name__}
+    if embedding:  # the embedding stage: k-means + assignment of the whole table, before the capture of the layer inputs
+        head.update({"ganq_embedding": True, "embedding_stage_s": round(proc.embedding_stage_seconds, 3),
+                     "embedding": type(model.get_input_embeddings()).__name__})
     return {"arch": arch, "layers": cfg.num_hidden_layers, "modules": len(proc.log), "bits": bits, **head,
             "ganq_iterations": iters, "calibration": f"{nsamples}x{seqlen} synthetic tokens",
             "total_s": round(dt, 3), "sum_module_quantize_s": round(quant_s, 3),
@@ -84,9 +88,10 @@ def main():
     ap.add_argument("--layers", type=int, default=0, help="truncate the model to this many layers (0 = all)")
     ap.add_argument("--lm-head", action="store_true", help="QuantizeConfig(lm_head=True): quantize the output head as well")
     ap.add_argument("--tied-embedding", default="untie", choices=["untie", "share"])
+    ap.add_argument("--embedding", action="store_true", help="QuantizeConfig(ganq_embedding=True): quantize the input embedding first")
     a = ap.parse_args()
     print(json.dumps(run(a.arch, a.nsamples, a.seqlen, a.batch, a.bits, a.iters, a.layers, lm_head=a.lm_head,
-                         tied_embedding=a.tied_embedding)))
+                         tied_embedding=a.tied_embedding, embedding=a.embedding)))
 
 
 if __name__ == "__main__":

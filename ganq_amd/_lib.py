@@ -107,6 +107,12 @@ SIGNATURES = {
     "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_lut_table_assign": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp]),
     "ganq_lut_table_lookup": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
+    "ganq_lut_table_bwd_lut_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_table_bwd_lut": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, ctypes.c_int, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_i64, _c_vp,
+                                              _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_embedding_bwd_lut_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_embedding_bwd_lut": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, ctypes.c_int, _c_vp, _c_i64, _c_i64, ctypes.c_int, _c_i64, _c_vp,
+                                                  _c_vp, _c_sz, _c_vp]),
     "ganq_outlier_cutoffs": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_extract": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
     "ganq_outlier_matmul": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -746,6 +752,56 @@ def lut_table_lookup(ids, qrows, lut, bits: int, out=None):
     _call("ganq_lut_table_lookup", (ids, qrows, lut, out), ids.data_ptr(), N, qrows.data_ptr(), lut.data_ptr(), code, m, n, int(bits),
           out.data_ptr(), _ST)
     return out
+
+
+def _lookup_bwd_lut(entry: str, ids, dy, q, m: int, n: int, bits: int, padding_idx):
+    """the shared host side of the two lookup gradients: flatten, sort, size the workspace, call `ganq_<entry>`"""
+    code = _act_dtype(dy, "dy")
+    if ids.dtype != torch.int64 or not ids.is_cuda:
+        raise GanqHipError(f"{entry}: ids must be an int64 cuda tensor")
+    if q.dtype != torch.int32 or q.dim() != 2 or not q.is_cuda:
+        raise GanqHipError(f"{entry}: the packed indices must be a 2-d int32 cuda tensor")
+    N = ids.numel()
+    if dy.numel() != N * n or (N and dy.shape[-1] != n):
+        raise GanqHipError(f"{entry}: dy {tuple(dy.shape)} does not fit ids {tuple(ids.shape)} x {n} columns")
+    dlut = torch.empty((m, 2 ** bits), dtype=torch.float32, device=dy.device)
+    if m == 0 or N == 0:  # (an empty sum; the library is not called, as lut_table_lookup does for an empty table)
+        return dlut.zero_()
+    ids = ids.reshape(-1).contiguous()
+    dy = dy.reshape(N, n).contiguous()  # (y.sum().backward() hands over a stride-0 gradient)
+    order = torch.sort(ids, stable=True).indices
+    pad = -1 if padding_idx is None else int(padding_idx)
+    if pad < -1:
+        raise GanqHipError(f"{entry}: padding_idx must be None or an id >= 0")
+    ws = _workspace(getattr(lib(), f"ganq_{entry}_workspace_bytes")(N, m, n, int(bits)), dy.device)
+    _call(f"ganq_{entry}", (ids, order, dy, q, dlut, ws), ids.data_ptr(), order.data_ptr(), N, dy.data_ptr(), code, q.data_ptr(), m, n, int(bits),
+          pad, dlut.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return dlut
+
+
+def lut_table_bwd_lut(ids, dy, qrows, bits: int, padding_idx=None):
+    """codebook gradient of `lut_table_lookup`: ids int64 (any shape), dy [..., n] fp16 / bf16, qrows int32 [m, n*bits/32] ->
+    dlut fp32 [m, 2^bits], dlut[id][v] = the sum of dy[p][j] over the positions p with ids[p] == id and the columns j with
+    Q[id][j] == v.  Ids outside [0, m) and the id `padding_idx` contribute nothing; rows and codes nothing selects are exactly 0.
+    Bitwise repeatable (no atomics); a sort, a memset and two launches, no host synchronisation."""
+    qrows = qrows.contiguous()
+    m = qrows.shape[0]
+    n = qrows.shape[1] * 32 // bits
+    if bits not in (2, 3, 4) or n * bits != qrows.shape[1] * 32:
+        raise GanqHipError(f"lut_table_bwd_lut: qrows {tuple(qrows.shape)} is no row-packed table at {bits} bits")
+    return _lookup_bwd_lut("lut_table_bwd_lut", ids, dy, qrows, m, n, bits, padding_idx)
+
+
+def lut_embedding_bwd_lut(ids, dy, qweight, in_features: int, bits: int, padding_idx=None):
+    """codebook gradient of `lut_embedding` (the lookup out of a packed head's stream): as `lut_table_bwd_lut` with
+    qweight int32 [n*bits/32, m] in the GPTQ column layout.  The head's outliers are frozen and get no gradient; the codes at
+    outlier positions count, as in `lut_linear_bwd_lut`."""
+    qweight = qweight.contiguous()
+    n = int(in_features)
+    m = qweight.shape[1]
+    if bits not in (2, 3, 4) or qweight.shape[0] * 32 != n * bits:
+        raise GanqHipError(f"lut_embedding_bwd_lut: qweight {tuple(qweight.shape)} does not fit {n} columns at {bits} bits")
+    return _lookup_bwd_lut("lut_embedding_bwd_lut", ids, dy, qweight, m, n, bits, padding_idx)
 
 
 SOLVE_REGIMES = ("none", "shared", "duo", "trio")  # GANQ_SOLVE_PLAN_*

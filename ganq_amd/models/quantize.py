@@ -380,6 +380,20 @@ def load_quantized(model: nn.Module, path: str) -> nn.Module:
     return model
 
 
+def train_codebooks(model: nn.Module, enabled: bool = True) -> List[nn.Parameter]:
+    """Switch the codebook of every packed module of `model` (GanqHipQuantLinear, GanqHipPackedEmbedding) with its
+    `train_codebook(enabled)` and return the codebook parameters (an empty list for enabled=False), in `named_modules()` order.  An
+    embedding that shares a packed head (GanqHipQuantEmbedding) owns no tensor: it trains through its head's `lut`, which then
+    collects the gradient of both the output projection and the lookup."""
+    params = []
+    for m in model.modules():
+        if isinstance(m, (GanqHipQuantLinear, GanqHipPackedEmbedding)):
+            m.train_codebook(enabled)
+            if enabled:
+                params.append(m.lut)
+    return params
+
+
 @torch.no_grad()
 def gptq_style_ppl(model: nn.Module, token_ids: torch.Tensor, seqlen: int = 2048) -> float:
     """token_ids: [1, total] (e.g. the wikitext-2-raw-v1 test split joined with "\\n\\n" and tokenized)."""

@@ -314,7 +314,52 @@ class _GanqLutLinearFn(torch.autograd.Function):
         return dx, dlut, None
 
 
-class GanqHipQuantEmbedding(nn.Module):
+class _PackedLookup:
+    """What the two packed embedding modules share.  A module provides `dtype`, `padding_idx`, `num_embeddings`, `_codebook()` (the
+    tensor that trains), `_lookup(ids)` (the inference launch) and `_lookup_bwd_lut(ids, dy)` (the codebook gradient of that launch)."""
+
+    def _as_dtype(self, slot: str, t: torch.Tensor) -> torch.Tensor:
+        """`t` in the output dtype: the buffer itself when it has it, else a copy converted once and kept until the buffer is
+        replaced or written in place (like GanqHipQuantLinear._lora_as)"""
+        t = t.detach()
+        if t.dtype == self.dtype:
+            return t
+        key = (self.dtype, t.data_ptr(), t._version)
+        cache = self.__dict__.get(slot)
+        if cache is None or cache[0] != key:
+            cache = (key, t.to(self.dtype).contiguous())
+            object.__setattr__(self, slot, cache)
+        return cache[1]
+
+    def _int64_ids(self, ids: torch.Tensor) -> torch.Tensor:
+        if not ids.is_cuda:
+            raise _lib.GanqHipError(f"{type(self).__name__} runs on the GPU only (no CPU fallback)")
+        if ids.dtype != torch.int64:
+            if ids.is_floating_point() or ids.dtype == torch.bool:
+                raise TypeError(f"{type(self).__name__}: ids must be integers, got {ids.dtype}")
+            ids = ids.long()
+        return ids
+
+    def _padding_id(self):
+        """`padding_idx` as an id in [0, num_embeddings), or None.  A negative one counts from the end and one outside the table is
+        refused, both as nn.Embedding does at construction."""
+        pad = self.padding_idx
+        if pad is None:
+            return None
+        pad = int(pad)
+        if not -self.num_embeddings <= pad < self.num_embeddings:
+            raise ValueError(f"{type(self).__name__}: padding_idx={pad} is outside a table of {self.num_embeddings} rows")
+        return pad + self.num_embeddings if pad < 0 else pad
+
+    def forward(self, ids: torch.Tensor):
+        ids = self._int64_ids(ids)
+        lut = self._codebook()
+        if torch.is_grad_enabled() and lut.requires_grad:
+            return _GanqLutLookupFn.apply(lut, ids, self)
+        return self._lookup(ids)
+
+
+class GanqHipQuantEmbedding(_PackedLookup, nn.Module):
     """The input embedding of a model whose embedding table is tied to a quantized output head (`QuantizeConfig.lm_head` with
     `ganq_tied_embedding="share"`): `forward(ids)` is row `id` of `head.dequantize_weight()`, gathered out of the head's packed
     stream by one HIP launch (csrc/lut_embedding.hip).  The head's outliers are part of the row; its adapter is not -- an adapter
@@ -323,8 +368,13 @@ class GanqHipQuantEmbedding(nn.Module):
     The module owns no tensor: it keeps an unregistered reference to the head and reads `qweight`, `lut` and the outlier CSR when it
     is called, so `state_dict()` gains no key, `.to()` of the model moves everything once and a checkpoint holds one table.  Ids of
     any shape give `[..., in_features]` in `dtype` (the dtype of the table this module replaced: fp16 or bf16); an id outside the
-    vocabulary gives a row of zeros.  No gradient flows through it: the output never has a grad_fn, neither the indices nor the
-    codebook are trained through the lookup."""
+    vocabulary gives a row of zeros.
+
+    Training: after `head.train_codebook(True)`, with grad mode on, `forward` goes through `_GanqLutLookupFn`: the same launch, the
+    same bits, and a backward (csrc/lut_table_backward.hip) that bins the incoming gradient of every occurrence of a row by the row's
+    own codes.  That gradient arrives in `head.lut.grad`, where autograd adds it to the term of the head's own forward: head and
+    embedding are one table.  The row `padding_idx` gets none (as in nn.Embedding); the indices and the head's outliers are frozen.
+    In every other case (inference, no_grad, a buffer codebook) the output has no grad_fn."""
 
     def __init__(self, head: GanqHipQuantLinear, dtype: torch.dtype = torch.float16, padding_idx=None):
         super().__init__()
@@ -342,38 +392,25 @@ class GanqHipQuantEmbedding(nn.Module):
     def head(self) -> GanqHipQuantLinear:
         return self._head
 
-    def _as_dtype(self, slot: str, t: torch.Tensor) -> torch.Tensor:
-        """`t` in the output dtype: the buffer itself when it has it, else a copy converted once and kept until the buffer is
-        replaced or written in place (like GanqHipQuantLinear._lora_as)"""
-        t = t.detach()
-        if t.dtype == self.dtype:
-            return t
-        key = (self.dtype, t.data_ptr(), t._version)
-        cache = self.__dict__.get(slot)
-        if cache is None or cache[0] != key:
-            cache = (key, t.to(self.dtype).contiguous())
-            object.__setattr__(self, slot, cache)
-        return cache[1]
+    def _codebook(self) -> torch.Tensor:
+        return self._head.lut
 
-    @torch.no_grad()
-    def forward(self, ids: torch.Tensor):
+    def _lookup(self, ids: torch.Tensor) -> torch.Tensor:
         head = self._head
-        if not ids.is_cuda:
-            raise _lib.GanqHipError("GanqHipQuantEmbedding runs on the GPU only (no CPU fallback)")
-        if ids.dtype != torch.int64:
-            if ids.is_floating_point() or ids.dtype == torch.bool:
-                raise TypeError(f"GanqHipQuantEmbedding: ids must be integers, got {ids.dtype}")
-            ids = ids.long()
         outl = None
         if head.outliers:
             outl = (head.outlier_rowptr, head.outlier_cols, self._as_dtype("_vals_cache", head.outlier_vals))
         return _lib.lut_embedding(ids, head.qweight, self._as_dtype("_lut_cache", head.lut), head.in_features, head.bits, outliers=outl)
 
+    def _lookup_bwd_lut(self, ids: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+        head = self._head
+        return _lib.lut_embedding_bwd_lut(ids, dy, head.qweight, head.in_features, head.bits, padding_idx=self._padding_id())
+
     def extra_repr(self) -> str:
         return f"{self.num_embeddings}, {self.embedding_dim}, bits={self._head.bits}, dtype={self.dtype}"
 
 
-class GanqHipPackedEmbedding(nn.Module):
+class GanqHipPackedEmbedding(_PackedLookup, nn.Module):
     """An input embedding quantized on its own (`QuantizeConfig.ganq_embedding`): it owns
       qweight_rows  int32 [num_embeddings, embedding_dim * bits / 32]   the row-packed indices: row `id` is the bit stream column `id`
                                                                         of a GanqHipQuantLinear's `qweight` would hold, so a
@@ -384,8 +421,14 @@ class GanqHipPackedEmbedding(nn.Module):
     vocabulary gives a row of zeros.  `padding_idx` is kept for the record and not read (nn.Embedding's forward does not read it
     either: it only masks the gradient).
 
-    No gradient flows through it, it has no adapter (an adapter corrects a layer's output under its inputs; a lookup has none) and
-    no outliers: the outlier split of `ganq_outlier_ratio` is not applied to embeddings."""
+    Training: `train_codebook(True)` turns `lut` into an fp32 nn.Parameter; with grad mode on `forward` then goes through
+    `_GanqLutLookupFn`: the same launch and the same bits (the codebook rounded to `dtype`, its gradient passing straight through that
+    rounding), and a backward (csrc/lut_table_backward.hip) that bins the incoming gradient of every occurrence of a row by the row's
+    own codes; the row `padding_idx` gets none, as in nn.Embedding.  The indices are frozen.  In every other case (inference, no_grad,
+    a buffer codebook) the output has no grad_fn.
+
+    It has no adapter (an adapter corrects a layer's output under its inputs; a lookup has none) and no outliers: the outlier split of
+    `ganq_outlier_ratio` is not applied to embeddings."""
 
     SUPPORTS_BITS = [2, 3, 4]
 
@@ -403,24 +446,57 @@ class GanqHipPackedEmbedding(nn.Module):
         self.register_buffer("qweight_rows", torch.zeros((self.num_embeddings, self.embedding_dim * self.bits // 32), dtype=torch.int32))
         self.register_buffer("lut", torch.zeros((self.num_embeddings, 2 ** self.bits), dtype=torch.float16))
 
-    _as_dtype = GanqHipQuantEmbedding._as_dtype
+    def train_codebook(self, enabled: bool = True):
+        """enabled: `lut` becomes an fp32 nn.Parameter (the master copy; each forward rounds it to `dtype` and its gradient passes
+        straight through that rounding).  False: back to an fp16 buffer, rounded once.  The name and so the state_dict key stay
+        `lut` (the semantics of GanqHipQuantLinear.train_codebook)."""
+        lut = self.lut.detach()
+        delattr(self, "lut")
+        if enabled:
+            self.lut = nn.Parameter(lut.to(torch.float32).clone())
+        else:
+            self.register_buffer("lut", lut.to(torch.float16).contiguous())
+        return self
 
-    @torch.no_grad()
-    def forward(self, ids: torch.Tensor):
-        if not ids.is_cuda:
-            raise _lib.GanqHipError("GanqHipPackedEmbedding runs on the GPU only (no CPU fallback)")
-        if ids.dtype != torch.int64:
-            if ids.is_floating_point() or ids.dtype == torch.bool:
-                raise TypeError(f"GanqHipPackedEmbedding: ids must be integers, got {ids.dtype}")
-            ids = ids.long()
+    def _codebook(self) -> torch.Tensor:
+        return self.lut
+
+    def _lookup(self, ids: torch.Tensor) -> torch.Tensor:
         return _lib.lut_table_lookup(ids, self.qweight_rows, self._as_dtype("_lut_cache", self.lut), self.bits)
 
+    def _lookup_bwd_lut(self, ids: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+        return _lib.lut_table_bwd_lut(ids, dy, self.qweight_rows, self.bits, padding_idx=self._padding_id())
+
     def dequantize_weight(self) -> torch.Tensor:
-        """the table [num_embeddings, embedding_dim] in `dtype`: a lookup of every id"""
-        return self.forward(torch.arange(self.num_embeddings, device=self.qweight_rows.device))
+        """the table [num_embeddings, embedding_dim] in `dtype`: a lookup of every id (no gradient)"""
+        return self._lookup(torch.arange(self.num_embeddings, device=self.qweight_rows.device))
 
     def extra_repr(self) -> str:
         return f"{self.num_embeddings}, {self.embedding_dim}, bits={self.bits}, dtype={self.dtype}"
+
+
+class _GanqLutLookupFn(torch.autograd.Function):
+    """out = F.embedding(ids, lut.gather(1, Q) (+ W_sparse)) of a packed embedding module with a HIP gradient for lut.  The forward is
+    the module's inference lookup (the codebook rounded to the table dtype); the gradient passes straight through that rounding."""
+
+    @staticmethod
+    def forward(ctx, lut_in, ids, module):
+        ctx.module = module
+        ctx.lut_dtype = lut_in.dtype
+        ctx.save_for_backward(ids)
+        return module._lookup(ids)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        module = ctx.module
+        (ids,) = ctx.saved_tensors
+        if dy.dtype != module.dtype:
+            dy = dy.to(module.dtype)
+        dlut = module._lookup_bwd_lut(ids, dy)
+        if dlut.dtype != ctx.lut_dtype:
+            dlut = dlut.to(ctx.lut_dtype)
+        return dlut, None, None
 
 
 __all__ = ["GanqHipQuantLinear", "GanqHipQuantEmbedding", "GanqHipPackedEmbedding", "BACKEND_GANQ_HIP"]

@@ -349,6 +349,31 @@ int ganq_lut_table_assign(const float* W, const float* T, int64_t m, int64_t n, 
 int ganq_lut_table_lookup(const int64_t* ids, int64_t N, const int32_t* qrows, const void* lut, int dtype, int64_t m, int64_t n,
                           int bits, void* out, void* stream);
 
+/* codebook gradient of the two lookups above (csrc/lut_table_backward.hip), the term autograd takes through
+ * F.embedding(ids, lut.gather(1, Q)) with respect to lut:
+ *   dlut [m, 2^bits] fp32 (16-byte aligned), dlut[id][v] = sum over the positions p with ids[p] == id and the columns j with
+ *   Q[id][j] == v of dy[p][j].  EVERY element of dlut is written: rows no id selects, codes no index of a row uses, an id outside
+ *   [0, m) and the id `padding_idx` (-1: none; nn.Embedding masks that row's gradient) contribute exactly 0; N == 0 gives zeros.
+ *   ganq_lut_table_bwd_lut takes the row-packed qrows [m, n * bits / 32] of ganq_lut_table_lookup, ganq_lut_embedding_bwd_lut the
+ *   GPTQ column layout qweight [n * bits / 32, m] of ganq_lut_embedding (the head's outliers are frozen: no gradient; the codes at
+ *   outlier positions count, as in ganq_lut_linear_bwd_lut).
+ *   ids int64 [N]; order int64 [N]: a STABLE ascending sort permutation of ids, computed by the caller (it is not trusted: an entry
+ *   outside [0, N) is skipped, never dereferenced; what a wrong permutation gives is unspecified but writes only dlut);
+ *   dy [N, n] (dtype 0 = fp16, 1 = bf16; 16-byte aligned), n a multiple of 32, bits 2, 3 or 4, N below 2^40 (-1 otherwise).
+ *   n == 0 or N == 0 needs no workspace (the query returns 0) and zero-fills dlut; m == 0 is a no-op.
+ * Deterministic: no floating-point atomics, the summation order is a function of (ids, dy) alone -- per position the columns in a
+ * fixed lane pattern, per id its positions in ascending order.  No host synchronisation, no allocation: a memset and two launches
+ * whatever the ids hold, capturable in a HIP graph.  The workspace (16-byte aligned) needs no initialisation; its size depends on
+ * the arguments alone (0 for N = 0) and is the same for both layouts. */
+size_t ganq_lut_table_bwd_lut_workspace_bytes(int64_t N, int64_t m, int64_t n, int bits);
+int ganq_lut_table_bwd_lut(const int64_t* ids, const int64_t* order, int64_t N, const void* dy, int dtype, const int32_t* qrows,
+                           int64_t m, int64_t n, int bits, int64_t padding_idx, float* dlut, void* workspace, size_t workspace_bytes,
+                           void* stream);
+size_t ganq_lut_embedding_bwd_lut_workspace_bytes(int64_t N, int64_t m, int64_t n, int bits);
+int ganq_lut_embedding_bwd_lut(const int64_t* ids, const int64_t* order, int64_t N, const void* dy, int dtype, const int32_t* qweight,
+                               int64_t m, int64_t n, int bits, int64_t padding_idx, float* dlut, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,

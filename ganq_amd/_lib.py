@@ -102,6 +102,9 @@ SIGNATURES = {
     "ganq_lut_linear_bwd_lut_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_linear_bwd_lut": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp,
                                                _c_sz, _c_vp]),
+    "ganq_lut_head_nll_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_head_nll": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp,
+                                         _c_vp, _c_vp, _c_sz, _c_vp]),
     "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -983,6 +986,32 @@ def lut_linear(x, qweight, lut, bias, bits: int, addend=None):
     _call("ganq_lut_linear_fwd", (x, qweight, lut, bias, y, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias), code, M, m, n, bits,
                                      y.data_ptr(), ws.data_ptr(), ws.numel(), _ST)
     return y
+
+
+def lut_head_nll(x, qweight, lut, bias, bits: int, targets):
+    """per-token negative log-likelihood straight from a packed head, the logits never written (csrc/lut_head_nll.hip):
+    x [M,n] fp16/bf16, qweight int32 [n*bits/32, m], lut [m,V], bias [m] or None, targets integer [M]
+    -> (nll, lse, tgt_logit), fp32 [M] each.  A row whose target lies outside [0, m) is ignored: nll = tgt_logit = 0."""
+    code = _act_dtype(x, "x")
+    if lut.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise GanqHipError("x, lut and bias must share one dtype")
+    if targets.is_floating_point() or targets.dtype == torch.bool or targets.dim() != 1 or targets.shape[0] != x.shape[0]:
+        raise GanqHipError(f"lut_head_nll: targets must be an integer tensor [M], got {targets.dtype} {tuple(targets.shape)}")
+    x, qweight, lut, targets = x.contiguous(), qweight.contiguous(), lut.contiguous(), targets.long().contiguous()
+    M, n = x.shape
+    m = lut.shape[0]
+    max_rows = ((1 << 31) - 1) // (2 * max(n, 1)) - 256  # see lut_linear
+    if M > max_rows:
+        step = max(256, max_rows // 256 * 256)
+        parts = [lut_head_nll(x[r:r + step], qweight, lut, bias, bits, targets[r:r + step]) for r in range(0, M, step)]
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+    out = torch.empty((3, M), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return out[0], out[1], out[2]
+    ws = _workspace(lib().ganq_lut_head_nll_workspace_bytes(M, m, n, bits), x.device)
+    _call("ganq_lut_head_nll", (x, qweight, lut, bias, targets, out, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias),
+          targets.data_ptr(), code, M, m, n, bits, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return out[0], out[1], out[2]
 
 
 def lut_linear_lora(x, qweight, lut, bias, bits: int, lora_A, lora_B, addend=None, outliers=None):

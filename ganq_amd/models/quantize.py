@@ -394,9 +394,36 @@ def train_codebooks(model: nn.Module, enabled: bool = True) -> List[nn.Parameter
     return params
 
 
+_POST_HEAD_LOGIT_ATTRS = ("final_logit_softcapping", "logit_scale", "logits_scaling")  # config entries that change the logits after the head
+
+
+def causal_lm_nll(model: nn.Module, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-token negative log-likelihood [batch, seq - 1] of a causal LM whose output head is a packed GanqHipQuantLinear, without
+    the [batch, seq, vocab] logits: the hidden states of `model.base_model(input_ids)[0]` go through `head.nll` (the fused HIP
+    kernel, or the chunked path of a head with outliers or an adapter).  Position t is scored against labels[:, t + 1]; labels
+    default to input_ids; a label outside the vocabulary (-100) gives 0.  Gradients follow `GanqHipQuantLinear.nll`.
+    Raises for a head that is not packed and for a config that scales or caps the logits after the head."""
+    head = model.get_output_embeddings() if hasattr(model, "get_output_embeddings") else None
+    if not isinstance(head, GanqHipQuantLinear):
+        raise TypeError(f"causal_lm_nll: the output head is {type(head).__name__}, not a GanqHipQuantLinear (quantize with "
+                        f"QuantizeConfig.lm_head=True)")
+    cfg = getattr(model, "config", None)
+    for attr in _POST_HEAD_LOGIT_ATTRS:
+        v = getattr(cfg, attr, None)
+        if v is not None and v != 1.0:
+            raise NotImplementedError(f"causal_lm_nll: the model's config sets {attr}={v}, applied to the logits after the head; "
+                                      f"the loss straight from the head would miss it")
+    labels = input_ids if labels is None else labels
+    if tuple(labels.shape) != tuple(input_ids.shape):
+        raise ValueError(f"causal_lm_nll: labels {tuple(labels.shape)} do not fit input_ids {tuple(input_ids.shape)}")
+    hidden = model.base_model(input_ids)[0]
+    return head.nll(hidden[:, :-1, :], labels[:, 1:].to(hidden.device))
+
+
 @torch.no_grad()
-def gptq_style_ppl(model: nn.Module, token_ids: torch.Tensor, seqlen: int = 2048) -> float:
-    """token_ids: [1, total] (e.g. the wikitext-2-raw-v1 test split joined with "\\n\\n" and tokenized)."""
+def gptq_style_ppl(model: nn.Module, token_ids: torch.Tensor, seqlen: int = 2048, fused_head: bool = False) -> float:
+    """token_ids: [1, total] (e.g. the wikitext-2-raw-v1 test split joined with "\\n\\n" and tokenized).
+    fused_head: the loss of every window straight from the packed head (`causal_lm_nll`): no [seqlen, vocab] logits."""
     dev = next(model.parameters()).device
     ids = token_ids.to(dev)
     nsamples = ids.numel() // seqlen
@@ -407,6 +434,9 @@ def gptq_style_ppl(model: nn.Module, token_ids: torch.Tensor, seqlen: int = 2048
     loss_fct = nn.CrossEntropyLoss()
     for i in range(nsamples):
         batch = ids[:, i * seqlen:(i + 1) * seqlen]
+        if fused_head:
+            nlls.append(causal_lm_nll(model, batch).mean() * seqlen)
+            continue
         logits = model(batch).logits
         shift_logits = logits[:, :-1, :].contiguous().float()
         shift_labels = batch[:, 1:]

@@ -43,6 +43,7 @@ from . import BaseQuantLinear
 
 BACKEND_GANQ_HIP = "ganq_hip"
 GEMV_MAX_ROWS = 64
+NLL_CHUNK_BYTES = 256 << 20  # logits (and their fp32 copy) a chunk of GanqHipQuantLinear.nll's chunked path may form; tests lower it
 
 
 class GanqHipQuantLinear(BaseQuantLinear):
@@ -251,6 +252,16 @@ class GanqHipQuantLinear(BaseQuantLinear):
             return _lib.lut_linear_outliers(x2, self.qweight, lut, bias, self.bits, self.outlier_rowptr, self.outlier_cols, vals)
         return _lib.lut_linear(x2, self.qweight, lut, bias, self.bits)
 
+    def _inference_forward(self, x2: torch.Tensor, lut: torch.Tensor = None):
+        """the inference call on x2 [M, in_features]: no grad_fn; the codebook (default: the layer's) rounded to the activation dtype"""
+        lut, bias = self.lut if lut is None else lut, self.bias
+        if lut.dtype != x2.dtype:
+            lut = lut.to(x2.dtype)
+            bias = None if bias is None else bias.to(x2.dtype)
+        if not self.adapter_rank:
+            return self._lut_forward(x2, lut, bias)
+        return self._lut_forward(x2, lut.detach(), bias, self._lora_as(x2.dtype))
+
     def forward(self, x: torch.Tensor):
         if not x.is_cuda:
             raise _lib.GanqHipError("GanqHipQuantLinear runs on the GPU only (no CPU fallback)")
@@ -259,22 +270,75 @@ class GanqHipQuantLinear(BaseQuantLinear):
         if not self.adapter_rank:
             if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad):
                 return _GanqLutLinearFn.apply(x2, self.lut, self).reshape(out_shape)
-            lut, bias = self.lut, self.bias
-            if lut.dtype != x.dtype:
-                lut = lut.to(x.dtype)
-                bias = None if bias is None else bias.to(x.dtype)
-            return self._lut_forward(x2, lut, bias).reshape(out_shape)
+            return self._inference_forward(x2).reshape(out_shape)
         if torch.is_grad_enabled() and (x.requires_grad or self.lut.requires_grad or self.lora_A.requires_grad
                                         or self.lora_B.requires_grad):
             # training: the adapter term in autograd around the LUT function (rank-r products, fp32)
             y = _GanqLutLinearFn.apply(x2, self.lut, self)
             t = x2.float() @ self.lora_A.float().t()
             return (y + (t @ self.lora_B.float().t()).to(y.dtype)).reshape(out_shape)
-        lut, bias = self.lut, self.bias
-        if lut.dtype != x.dtype:
-            lut = lut.to(x.dtype)
-            bias = None if bias is None else bias.to(x.dtype)
-        return self._lut_forward(x2, lut.detach(), bias, self._lora_as(x.dtype)).reshape(out_shape)
+        return self._inference_forward(x2).reshape(out_shape)
+
+    # ---- per-token negative log-likelihood of the layer as an output head, without the full logits
+    def _nll_chunk_rows(self, itemsize: int) -> int:
+        """rows per chunk of the chunked path: the chunk's logits and their fp32 copy stay under NLL_CHUNK_BYTES, at least 64 rows"""
+        return max(64, NLL_CHUNK_BYTES // (self.out_features * (itemsize + 4)))
+
+    def _nll_forward(self, x2: torch.Tensor, targets: torch.Tensor, fused: bool, lut: torch.Tensor = None):
+        """(nll, lse) fp32 [M] of x2 [M, in_features] and int64 targets [M]; no graph is built"""
+        with torch.no_grad():
+            if fused:
+                lut, bias = self.lut if lut is None else lut, self.bias
+                if lut.dtype != x2.dtype:
+                    lut = lut.to(x2.dtype)
+                    bias = None if bias is None else bias.to(x2.dtype)
+                nll, lse, _ = _lib.lut_head_nll(x2, self.qweight, lut.detach(), bias, self.bits, targets)
+                return nll, lse
+            M = x2.shape[0]
+            nll = torch.empty(M, dtype=torch.float32, device=x2.device)
+            lse = torch.empty(M, dtype=torch.float32, device=x2.device)
+            step = self._nll_chunk_rows(x2.element_size())
+            for r in range(0, M, step):
+                logits = self._inference_forward(x2[r:r + step], lut).float()
+                t = targets[r:r + step]
+                hit = (t >= 0) & (t < self.out_features)
+                l = torch.logsumexp(logits, dim=-1)
+                tl = logits.gather(1, t.clamp(0, self.out_features - 1).unsqueeze(1)).squeeze(1)
+                lse[r:r + step] = l
+                nll[r:r + step] = torch.where(hit, l - tl, torch.zeros_like(l))
+            return nll, lse
+
+    def nll(self, x: torch.Tensor, targets: torch.Tensor, fused=None):
+        """Per-token negative log-likelihood -log softmax(layer(x))[target] of the layer as an output head: x [..., in_features],
+        integer targets of shape x.shape[:-1] -> fp32 of that shape.  A target outside [0, out_features) (-100 included) marks an
+        ignored token: 0.  The [tokens, out_features] logits are never formed:
+          fused (the default of a layer with neither outliers nor an adapter; True on any other layer raises): one library call
+            (csrc/lut_head_nll.hip) reduces the fp32 logits tile by tile, nothing of them is written;
+          chunked (fused=False, and the default of every other layer): rows go through the ordinary forward in chunks whose logits
+            stay under NLL_CHUNK_BYTES, torch.logsumexp on the fp32 chunk.
+        With grad mode on and x or lut requiring grad the call goes through `_GanqLutNllFn`: dx and dlut from the HIP gradients of
+        the ordinary forward, the logits recomputed chunk by chunk.  An adapter in training raises: train it through forward()."""
+        if not x.is_cuda:
+            raise _lib.GanqHipError("GanqHipQuantLinear runs on the GPU only (no CPU fallback)")
+        if targets.is_floating_point() or targets.dtype == torch.bool:
+            raise TypeError(f"GanqHipQuantLinear.nll: targets must be integers, got {targets.dtype}")
+        if tuple(targets.shape) != tuple(x.shape[:-1]):
+            raise ValueError(f"GanqHipQuantLinear.nll: targets {tuple(targets.shape)} do not fit x {tuple(x.shape)}")
+        can_fuse = not self.outliers and not self.adapter_rank
+        if fused is None:
+            fused = can_fuse
+        elif fused and not can_fuse:
+            raise ValueError("GanqHipQuantLinear.nll: fused=True serves a layer with neither outliers nor an adapter; this layer takes "
+                             "the chunked path (fused=False or None)")
+        x2 = x.reshape(-1, self.in_features)
+        t1 = targets.reshape(-1).to(device=x.device, dtype=torch.int64)
+        if torch.is_grad_enabled():
+            if self.adapter_rank and (self.lora_A.requires_grad or self.lora_B.requires_grad):
+                raise NotImplementedError("GanqHipQuantLinear.nll has no gradient for a trainable adapter: train lora_A / lora_B through "
+                                          "the ordinary forward, F.cross_entropy(layer(x).float(), targets)")
+            if x.requires_grad or self.lut.requires_grad:
+                return _GanqLutNllFn.apply(x2, self.lut, t1, self, bool(fused)).reshape(targets.shape)
+        return self._nll_forward(x2, t1, bool(fused))[0].reshape(targets.shape)
 
 
 class _GanqLutLinearFn(torch.autograd.Function):
@@ -295,23 +359,76 @@ class _GanqLutLinearFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        layer = ctx.layer
         lut, x2 = ctx.saved_tensors
-        dy = dy.contiguous()  # (y.sum().backward() hands over a stride-0 gradient)
-        if dy.dtype != lut.dtype:
-            dy = dy.to(lut.dtype)
-        dx = dlut = None
-        if ctx.needs_input_grad[0]:
-            addend = None
-            if layer.outliers:  # dy @ W_sparse in fp32, added before the kernel's one rounding
-                rowptr_t, cols_t, vals_t = layer._outliers_t(dy.dtype)
-                addend = _lib.outlier_matmul(dy, rowptr_t, cols_t, vals_t, layer.in_features)
-            dx = _lib.lut_linear_bwd_input(dy, layer.qweight, lut, layer.bits, addend)
-        if ctx.needs_input_grad[1]:
-            dlut = _lib.lut_linear_bwd_lut(dy, x2, layer.qweight, layer.bits, layer.out_features)
-            if dlut.dtype != ctx.lut_dtype:
-                dlut = dlut.to(ctx.lut_dtype)
+        dx, dlut = _lut_linear_backward(ctx.layer, dy, lut, x2, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if dlut is not None and dlut.dtype != ctx.lut_dtype:
+            dlut = dlut.to(ctx.lut_dtype)
         return dx, dlut, None
+
+
+def _lut_linear_backward(layer, dy, lut, x2, need_dx: bool, need_dlut: bool):
+    """the HIP gradients of y = F.linear(x, lut.gather(1, Q) + W_sparse) for dy [M, out_features]: dx in lut's dtype (one rounding)
+    and dlut fp32 [out_features, V]; `lut` in the activation dtype, x2 [M, in_features] (only read for dlut)"""
+    dy = dy.contiguous()  # (y.sum().backward() hands over a stride-0 gradient)
+    if dy.dtype != lut.dtype:
+        dy = dy.to(lut.dtype)
+    dx = dlut = None
+    if need_dx:
+        addend = None
+        if layer.outliers:  # dy @ W_sparse in fp32, added before the kernel's one rounding
+            rowptr_t, cols_t, vals_t = layer._outliers_t(dy.dtype)
+            addend = _lib.outlier_matmul(dy, rowptr_t, cols_t, vals_t, layer.in_features)
+        dx = _lib.lut_linear_bwd_input(dy, layer.qweight, lut, layer.bits, addend)
+    if need_dlut:
+        dlut = _lib.lut_linear_bwd_lut(dy, x2, layer.qweight, layer.bits, layer.out_features)
+    return dx, dlut
+
+
+class _GanqLutNllFn(torch.autograd.Function):
+    """nll = layer.nll(x, targets) for x2 [M, in_features] with the HIP gradients of the ordinary forward for x and lut.  The forward
+    is the inference call (fused or chunked); the backward walks the row chunks of the chunked path in ascending order: it recomputes a
+    chunk's logits with the inference forward, forms g = (softmax - onehot(target)) * dnll in fp32 (0 for ignored rows), rounds it once
+    to the activation dtype and hands it to `_lut_linear_backward`; dlut accumulates in fp32 over the chunks.  Deterministic.
+    The softmax is normalised by the recomputed chunk itself, not by the forward's lse: the fused forward reduces UNROUNDED logits,
+    the recomputed ones are rounded to the activation dtype, and exp(rounded - lse of the unrounded) misses a row sum of 1 by the
+    averaged rounding error (1e-4 relative, measured) -- a gradient component along the all-ones direction that is not there."""
+
+    @staticmethod
+    def forward(ctx, x2, lut_in, targets, layer, fused):
+        nll, _ = layer._nll_forward(x2, targets, fused, lut_in)
+        ctx.layer = layer
+        ctx.save_for_backward(x2, lut_in, targets)
+        return nll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dnll):
+        layer = ctx.layer
+        x2, lut_in, targets = ctx.saved_tensors
+        need_dx, need_dlut = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        lut = lut_in.detach() if lut_in.dtype == x2.dtype else lut_in.detach().to(x2.dtype)
+        m, M = layer.out_features, x2.shape[0]
+        dnll = dnll.float()
+        step = layer._nll_chunk_rows(x2.element_size())
+        dxs, dlut = [], None
+        for r in range(0, M, step):
+            xc, t = x2[r:r + step], targets[r:r + step]
+            g = torch.softmax(layer._inference_forward(xc, lut).float(), dim=-1)
+            hit = (t >= 0) & (t < m)
+            g.scatter_add_(1, t.clamp(0, m - 1).unsqueeze(1), -hit.to(g.dtype).unsqueeze(1))
+            g = (g * torch.where(hit, dnll[r:r + step], torch.zeros_like(dnll[r:r + step])).unsqueeze(1)).to(x2.dtype)
+            dx_c, dlut_c = _lut_linear_backward(layer, g, lut, xc, need_dx, need_dlut)
+            if need_dx:
+                if layer.adapter_rank:  # a frozen adapter: its rank-r products in fp32, as the training forward composes them
+                    gf = g.float()
+                    dx_c = (dx_c.float() + (gf @ layer.lora_B.detach().float()) @ layer.lora_A.detach().float()).to(dx_c.dtype)
+                dxs.append(dx_c)
+            if need_dlut:
+                dlut = dlut_c if dlut is None else dlut.add_(dlut_c)
+        dx = torch.cat(dxs, dim=0) if need_dx else None
+        if dlut is not None and dlut.dtype != lut_in.dtype:
+            dlut = dlut.to(lut_in.dtype)
+        return dx, dlut, None, None, None
 
 
 class _PackedLookup:

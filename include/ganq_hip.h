@@ -374,6 +374,22 @@ int ganq_lut_embedding_bwd_lut(const int64_t* ids, const int64_t* order, int64_t
                                int64_t m, int64_t n, int bits, int64_t padding_idx, float* dlut, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- per-token negative log-likelihood straight from a packed head (csrc/lut_head_nll.hip): the logits
+ *   logits[M,m] = x[M,n] @ dequant(qweight, lut)^T (+ bias)   (fp32, not rounded)
+ * are never written.  Same qweight / lut / bias layout and dtypes as ganq_lut_linear_fwd; bits 2, 3 or 4, n a multiple of 32, any
+ * M >= 1 and m >= 1; x 16-byte aligned; targets int64 [M].  Outputs, fp32 [M] each:
+ *   lse[row] = log sum_o exp(logits[row][o]),  tgt_logit[row] = logits[row][targets[row]],  nll[row] = lse[row] - tgt_logit[row].
+ * A row whose target lies outside [0, m) (-100 or anything else) is ignored: nll = tgt_logit = 0, lse still written.
+ * Two launches: 256 x 128 tiles of the fused LUT-dequant GEMM reduce every row to (max, sum of exp) per feature tile, a second
+ * kernel merges the tiles in a fixed order.  No atomics, no memset, no host synchronisation: the same bytes on every call,
+ * capturable in a HIP graph.  The workspace (8-byte aligned, no initialisation) holds 8 bytes per row and 128-feature tile plus
+ * 4 bytes per row: 8 * M * ceil(m / 128) + 4 * M.  Error codes as ganq_lut_linear_fwd (-4: workspace too small, nothing written;
+ * -1: x or qweight beyond the 2 GB window of the 32-bit buffer offsets -- split the rows of x over several calls). */
+size_t ganq_lut_head_nll_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
+int ganq_lut_head_nll(const void* x, const int32_t* qweight, const void* lut, const void* bias, const int64_t* targets, int dtype,
+                      int64_t M, int64_t m, int64_t n, int bits, float* nll, float* lse, float* tgt_logit, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,

@@ -105,6 +105,10 @@ SIGNATURES = {
     "ganq_lut_head_nll_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "ganq_lut_head_nll": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp,
                                          _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_head_pick_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "ganq_lut_head_pick": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_float, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int,
+                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_debug_head_pick_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -1012,6 +1016,45 @@ def lut_head_nll(x, qweight, lut, bias, bits: int, targets):
     _call("ganq_lut_head_nll", (x, qweight, lut, bias, targets, out, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias),
           targets.data_ptr(), code, M, m, n, bits, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(), _ST)
     return out[0], out[1], out[2]
+
+
+def lut_head_pick(x, qweight, lut, bias, bits: int, noise=None, inv_t: float = 1.0):
+    """next token straight from a packed head, the logits never written (csrc/lut_head_pick.hip):
+    x [M,n] fp16/bf16, qweight int32 [n*bits/32, m], lut [m,V], bias [m] or None, noise fp32 [M,m] or None, inv_t > 0
+    -> (token int64, score, lse, logprob fp32), [M] each: token = the smallest argmax of s + noise with s = logits * inv_t,
+    score = s[token], lse = logsumexp(s), logprob = score - lse.  noise=None, inv_t=1 is greedy; noise = -log(Exp(1)) samples."""
+    code = _act_dtype(x, "x")
+    if lut.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise GanqHipError("x, lut and bias must share one dtype")
+    M, n = x.shape
+    m = lut.shape[0]
+    if noise is not None and (noise.dtype != torch.float32 or tuple(noise.shape) != (M, m)):
+        raise GanqHipError(f"lut_head_pick: noise must be an fp32 [M, out_features] tensor, got {noise.dtype} {tuple(noise.shape)}")
+    x, qweight, lut = x.contiguous(), qweight.contiguous(), lut.contiguous()
+    noise = None if noise is None else noise.contiguous()
+    max_rows = ((1 << 31) - 1) // (2 * max(n, 1)) - 256  # see lut_linear
+    if M > max_rows:
+        step = max(256, max_rows // 256 * 256)
+        parts = [lut_head_pick(x[r:r + step], qweight, lut, bias, bits, None if noise is None else noise[r:r + step], inv_t)
+                 for r in range(0, M, step)]
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
+    token = torch.empty(M, dtype=torch.int64, device=x.device)
+    out = torch.empty((3, M), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return token, out[0], out[1], out[2]
+    ws = _workspace(lib().ganq_lut_head_pick_workspace_bytes(M, m, n, bits), x.device)
+    _call("ganq_lut_head_pick", (x, qweight, lut, bias, noise, token, out, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(), _ptr(bias),
+          _ptr(noise), float(inv_t), code, M, m, n, bits, token.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+          ws.data_ptr(), ws.numel(), _ST)
+    return token, out[0], out[1], out[2]
+
+
+def debug_head_pick_plan(M: int, m: int, n: int, bits: int):
+    """(tile launches, feature blocks, merge workgroups, [RT of every tile launch]) of lut_head_pick; host only"""
+    launches = -(-int(M) // 64)
+    out = (ctypes.c_int * (3 + launches))()
+    _check(lib().ganq_debug_head_pick_plan(M, m, n, bits, ctypes.cast(out, _c_vp), 3 + launches), "ganq_debug_head_pick_plan")
+    return out[0], out[1], out[2], list(out[3:3 + launches])
 
 
 def lut_linear_lora(x, qweight, lut, bias, bits: int, lora_A, lora_B, addend=None, outliers=None):

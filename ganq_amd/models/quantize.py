@@ -420,6 +420,29 @@ def causal_lm_nll(model: nn.Module, input_ids: torch.Tensor, labels: Optional[to
     return head.nll(hidden[:, :-1, :], labels[:, 1:].to(hidden.device))
 
 
+def causal_lm_next_token(model: nn.Module, input_ids: torch.Tensor, temperature: float = 0.0, generator=None, **base_model_kwargs):
+    """The next token of a causal LM whose output head is a packed GanqHipQuantLinear, without the [batch, vocab] logits:
+    `model.base_model(input_ids, **base_model_kwargs)` runs and the hidden state of the last position goes through `head.pick`
+    (greedy at temperature 0, a sample from softmax(logits / temperature) drawn with `generator` otherwise).
+    -> (token int64 [batch], logprob fp32 [batch], the base model's outputs -- so a caller can carry `past_key_values`).  No graph is
+    built; the gradient of logprob is taken in the training pass, through `causal_lm_nll`.
+    Raises for a head that is not packed and for a config that scales or caps the logits after the head."""
+    head = model.get_output_embeddings() if hasattr(model, "get_output_embeddings") else None
+    if not isinstance(head, GanqHipQuantLinear):
+        raise TypeError(f"causal_lm_next_token: the output head is {type(head).__name__}, not a GanqHipQuantLinear (quantize with "
+                        f"QuantizeConfig.lm_head=True)")
+    cfg = getattr(model, "config", None)
+    for attr in _POST_HEAD_LOGIT_ATTRS:
+        v = getattr(cfg, attr, None)
+        if v is not None and v != 1.0:
+            raise NotImplementedError(f"causal_lm_next_token: the model's config sets {attr}={v}, applied to the logits after the head; "
+                                      f"the token straight from the head would miss it")
+    with torch.no_grad():
+        outputs = model.base_model(input_ids, **base_model_kwargs)
+        token, logprob = head.pick(outputs[0][:, -1, :], temperature=temperature, generator=generator)
+    return token, logprob, outputs
+
+
 @torch.no_grad()
 def gptq_style_ppl(model: nn.Module, token_ids: torch.Tensor, seqlen: int = 2048, fused_head: bool = False) -> float:
     """token_ids: [1, total] (e.g. the wikitext-2-raw-v1 test split joined with "\\n\\n" and tokenized).

@@ -34,6 +34,8 @@ call only carries the dequantised nn.Linear, the indices/codebook are either pas
 (`ganq_indices=`, `ganq_codebook=`, what ganq_amd's processor does) or recovered from the weight itself -- a
 GANQ weight row has at most 2^bits distinct values, so sorted-unique values are the codebook.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -339,6 +341,65 @@ class GanqHipQuantLinear(BaseQuantLinear):
             if x.requires_grad or self.lut.requires_grad:
                 return _GanqLutNllFn.apply(x2, self.lut, t1, self, bool(fused)).reshape(targets.shape)
         return self._nll_forward(x2, t1, bool(fused))[0].reshape(targets.shape)
+
+    # ---- the next token of the layer as an output head, without the full logits
+    @torch.no_grad()
+    def pick(self, x: torch.Tensor, temperature: float = 0.0, generator=None, noise: torch.Tensor = None, fused=None):
+        """The next token of the layer as an output head: x [..., in_features] -> (token int64, logprob fp32) of shape x.shape[:-1].
+          temperature == 0: greedy, token = argmax of the logits (the smallest index among equals in the fused path), logprob its
+            plain log-softmax value;
+          temperature > 0: a token sampled from softmax(logits / temperature) by the Gumbel-max rule, token = argmax of
+            logits / temperature + noise, logprob = log_softmax(logits / temperature)[token].  noise: fp32 [..., out_features]; by
+            default -log(E) with E = torch.empty(M, out_features).exponential_(generator=generator), clamped away from 0.
+          fused (the default of a layer with neither outliers nor an adapter; True on any other layer raises): one library call
+            (csrc/lut_head_pick.hip) reduces the unrounded fp32 logits tile by tile, the same logits `nll` uses: at temperature 1
+            logprob and -nll(x, token) are the same number up to the order of the sums;
+          composition (fused=False, and the default of every other layer): rows go through the ordinary forward in chunks whose
+            logits stay under NLL_CHUNK_BYTES, torch.logsumexp / torch.argmax on the fp32 chunk; ties are torch.argmax's.
+        The call always runs under torch.no_grad() and its outputs carry no graph: the gradient of a rollout's logprob is taken in
+        the training pass, through nll(x, token)."""
+        if not x.is_cuda:
+            raise _lib.GanqHipError("GanqHipQuantLinear runs on the GPU only (no CPU fallback)")
+        temperature = float(temperature)
+        if not math.isfinite(temperature) or temperature < 0:
+            raise ValueError(f"GanqHipQuantLinear.pick: temperature must be finite and >= 0, got {temperature}")
+        can_fuse = not self.outliers and not self.adapter_rank
+        if fused is None:
+            fused = can_fuse
+        elif fused and not can_fuse:
+            raise ValueError("GanqHipQuantLinear.pick: fused=True serves a layer with neither outliers nor an adapter; this layer takes "
+                             "the composition (fused=False or None)")
+        shape = tuple(x.shape[:-1])
+        x2 = x.detach().reshape(-1, self.in_features)
+        M, m = x2.shape[0], self.out_features
+        if noise is not None:
+            if noise.dtype != torch.float32:
+                raise TypeError(f"GanqHipQuantLinear.pick: noise must be float32, got {noise.dtype}")
+            if tuple(noise.shape) != shape + (m,):
+                raise ValueError(f"GanqHipQuantLinear.pick: noise {tuple(noise.shape)} does not fit x {tuple(x.shape)} and {m} out_features")
+            noise = noise.detach().to(x.device).reshape(M, m)
+        inv_t = 1.0
+        if temperature > 0:
+            inv_t = 1.0 / temperature
+            if noise is None:
+                e = torch.empty(M, m, dtype=torch.float32, device=x.device).exponential_(generator=generator)
+                noise = e.clamp_min_(torch.finfo(torch.float32).tiny).log_().neg_()
+        if fused:
+            lut, bias = self.lut.detach(), self.bias
+            if lut.dtype != x2.dtype:
+                lut = lut.to(x2.dtype)
+                bias = None if bias is None else bias.to(x2.dtype)
+            token, _, _, logprob = _lib.lut_head_pick(x2, self.qweight, lut, bias, self.bits, noise, inv_t)
+            return token.reshape(shape), logprob.reshape(shape)
+        token = torch.empty(M, dtype=torch.int64, device=x2.device)
+        logprob = torch.empty(M, dtype=torch.float32, device=x2.device)
+        step = self._nll_chunk_rows(x2.element_size())
+        for r in range(0, M, step):
+            s = self._inference_forward(x2[r:r + step]).float() * inv_t
+            t = torch.argmax(s if noise is None else s + noise[r:r + step], dim=-1)
+            token[r:r + step] = t
+            logprob[r:r + step] = s.gather(1, t.unsqueeze(1)).squeeze(1) - torch.logsumexp(s, dim=-1)
+        return token.reshape(shape), logprob.reshape(shape)
 
 
 class _GanqLutLinearFn(torch.autograd.Function):

@@ -390,6 +390,35 @@ int ganq_lut_head_nll(const void* x, const int32_t* qweight, const void* lut, co
                       int64_t M, int64_t m, int64_t n, int bits, float* nll, float* lse, float* tgt_logit, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- next token straight from a packed head (csrc/lut_head_pick.hip): the decode-side counterpart of ganq_lut_head_nll.  For
+ * x [M, n], a packed head (qweight, lut, bias) of m features, inv_t > 0 and an optional noise [M, m] (finite fp32, or NULL):
+ *   l[r][o] = x[r] . dequant(qweight, lut)[o] (+ bias[o])      fp32, never rounded, never written
+ *   s[r][o] = l[r][o] * inv_t
+ *   lse[r]  = log sum_o exp(s[r][o])
+ *   z[r][o] = s[r][o] + noise[r][o]        (noise absent: z = s)
+ *   token[r]   = the SMALLEST o with z[r][o] = max_o z[r][o]
+ *   score[r]   = s[r][token[r]]            (without the noise)
+ *   logprob[r] = score[r] - lse[r]
+ * Only valid features (o < m) take part.  Greedy: noise = NULL, inv_t = 1.  Exact sampling from softmax(l / T): inv_t = 1 / T and
+ * noise = -log(E), E ~ Exp(1) iid (Gumbel-max).  The library draws nothing: the call is deterministic and the random numbers are
+ * the caller's.  Same qweight / lut / bias layout and dtypes as ganq_lut_linear_fwd; bits 2, 3 or 4, n a multiple of 32, any
+ * M >= 1 and m >= 1; x 16-byte aligned.  Outputs [M]: token int64, score / lse / logprob fp32.
+ * One tile launch per 64 rows (a workgroup of 4 waves owns 128 features and all of in_features and leaves one record
+ * (max, sum of exp, best z, its s, its index) per row), then one merge launch: a wave per row, its lanes over 64 contiguous
+ * ranges of the feature blocks in ascending order.  No atomics, no memset, no host synchronisation: the same bytes on every call,
+ * capturable in a HIP graph.  The workspace (16-byte
+ * aligned, no initialisation) holds 20 bytes per row and 128-feature block: 20 * M * ceil(m / 128), whatever n and bits are.
+ * Error codes: -2 bits outside {2, 3, 4}, n not a multiple of 32, unknown dtype, inv_t not finite or <= 0; -1 M < 0, or x or
+ * qweight beyond the 2 GB window of the 32-bit offsets (split the rows of x over several calls); -3 null pointer; -4 workspace
+ * too small.  A refused call writes nothing.
+ * ganq_debug_head_pick_plan (host only): out = { tile launches, feature blocks, workgroups of the merge launch, then the row tiles
+ * RT = ceil(rows / 16) of each tile launch, as many as out_len leaves room for }; out_len >= 3. */
+size_t ganq_lut_head_pick_workspace_bytes(int64_t M, int64_t m, int64_t n, int bits);
+int ganq_lut_head_pick(const void* x, const int32_t* qweight, const void* lut, const void* bias, const float* noise, float inv_t,
+                       int dtype, int64_t M, int64_t m, int64_t n, int bits, int64_t* token, float* score, float* lse, float* logprob,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int ganq_debug_head_pick_plan(int64_t M, int64_t m, int64_t n, int bits, int* out, int out_len);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,

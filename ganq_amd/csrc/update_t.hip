@@ -559,7 +559,12 @@ __global__ __launch_bounds__(TW * 64) void onehot_accum_kernel(const int8_t* __r
 constexpr int W4_SU = 128;   // u per slice
 constexpr int W4_NST = 4;    // LDS stages
 constexpr int W4_RING = W4_NST * 4 * 32 * W4_SU;  // bytes of the ring with four planes (the extension's two planes use half of every stage)
-constexpr size_t W4_LDS = (size_t)W4_RING + 4 * 8 * 256 * sizeof(long long);
+// bucket sums [wave][row][a * W4_NB + b]: 16 buckets b per (row, a) and one more that nobody reads, where a column whose code is
+// outside 0 .. 15 adds its sums.  The odd count is also the padding: the 16 lanes of a quarter wave hold the 16 codes a of one row
+// and add into the same b, 136 bytes apart -- 16 different pairs of banks
+constexpr int W4_NB = 17;
+constexpr int W4_MROW = 4 * 8 * 16 * W4_NB * (int)sizeof(long long);
+constexpr size_t W4_LDS = (size_t)W4_RING + W4_MROW;
 
 struct W4It {  // (chunk, slice) in the flat slice sequence of a workgroup
     int c, s;
@@ -579,8 +584,11 @@ __device__ __forceinline__ void w4_mfma(v16i& acc, const v4i& a, const v4i& b) {
     if constexpr (FIRST) asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
     else asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void w4_mfma_zero(v16i& acc, const v4i& z) {  // acc = 0, born in an accumulation register
-    asm volatile("s_nop 4\n\tv_mfma_i32_32x32x32_i8 %0, %1, %1, 0" : "=a"(acc) : "v"(z));
+// a chunk's first matrix instruction of an accumulator tile: acc = a b, born in an accumulation register (no zeroing instruction)
+template <bool FIRST>
+__device__ __forceinline__ void w4_mfma_open(v16i& acc, const v4i& a, const v4i& b) {
+    if constexpr (FIRST) asm volatile("s_nop 1\n\tv_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
 }
 // Loads and LDS atomics the COMPILER DOES NOT COUNT: with LDS-DMA in flight hipcc waits for vmcnt(0) in front of every use of a
 // loaded register and of every LDS atomic (it cannot tell what the DMA may still write), which would drain the ring once per slice.
@@ -591,13 +599,17 @@ __device__ __forceinline__ uint32_t w4_load_u32(const void* sbase, uint32_t voff
     asm volatile("global_load_dword %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
     return r;
 }
-__device__ __forceinline__ uint32_t w4_load_u8(const void* sbase, uint32_t voff) {
-    uint32_t r;
-    asm volatile("global_load_ubyte %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
-    return r;
-}
-__device__ __forceinline__ void w4_lds_add_u64(uint32_t addr, unsigned long long v) {
-    asm volatile("ds_add_u64 %0, %1" : : "v"(addr), "v"(v) : "memory");
+// row pair p of the wave: 2 p rows behind `addr`, in the instruction's immediate offset (p is a constant once the bucketing loop is
+// unrolled: the switch folds away)
+__device__ __forceinline__ void w4_lds_add_u64(uint32_t addr, int p, uint32_t lo, uint32_t hi) {
+    const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+#define W4_ADD_AT(P) \
+    case P: asm volatile("ds_add_u64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"((P) * 2 * 16 * W4_NB * 8) : "memory"); break;
+    switch (p) {
+        W4_ADD_AT(0) W4_ADD_AT(1) W4_ADD_AT(2) W4_ADD_AT(3)
+        default: __builtin_unreachable();
+    }
+#undef W4_ADD_AT
 }
 
 template <int NPL, int P0>
@@ -612,14 +624,19 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     static_assert(NPL >= 2 && NPL <= 4 && NI * 4 * 1024 == ST && NI * HSTEP <= 4, "a slice is NI LDS-DMA instructions per wave");
     extern __shared__ __align__(1024) char w4_smem[];
     char* const ring = w4_smem;
-    long long(*Mrow)[8][256] = reinterpret_cast<long long(*)[8][256]>(w4_smem + W4_RING);  // [wave][row][a * 16 + b]
+    long long(*Mrow)[8][16 * W4_NB] = reinterpret_cast<long long(*)[8][16 * W4_NB]>(w4_smem + W4_RING);  // [wave][row][a * W4_NB + b]
     const int8_t* planes = planes_all + (int64_t)P0 * n * nq;
     long long st_pro = 0, st_loop = 0, st_flush = 0;
     long long st_t0 = __builtin_amdgcn_s_memtime();
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: the LDS-DMA destinations are scalar arithmetic)
-    // v_mfma_i32_32x32x32_i8 as in onehot_accum_body: A rows = (row of the pair, code), B columns = the chunk's 32 v
+    // v_mfma_i32_32x32x32_i8 with the operands of onehot_accum_body SWAPPED: A rows = the chunk's 32 v, B columns = (row of the pair,
+    // code).  (Both operands have lane l hold row / column l & 31 and k bytes 16 (l >> 5) .. + 15, so the fragments are the same.)
+    // The tile comes out transposed: lane l holds (row r2, code a16) for good and its 16 registers hold 16 columns v.  In the
+    // bucketing pass the lanes of an instruction then add into DIFFERENT (row, a) -- with (row, a) across the registers and v
+    // across the lanes, the lanes of a quarter wave whose columns share a code added to the same address, and an LDS atomic
+    // takes them one after the other (profiles/accum_sched_v1.txt: 92 cycles per ds_add_u64, whatever D)
     const int i32 = lane & 31, kb = lane >> 5;
     const int r2 = i32 >> 4, a16 = i32 & 15;
     const int nrg = (m + 31) / 32;
@@ -629,7 +646,9 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     int mrow[4];  // the row whose masks this lane expands, per row pair
 #pragma unroll
     for (int p = 0; p < 4; ++p) mrow[p] = min(row0 + 2 * p + r2, m - 1);
-    for (int i = lane; i < 8 * 256; i += 64) Mrow[wv][i >> 8][i & 255] = 0;
+    for (int i = lane; i < 8 * 16 * W4_NB; i += 64) (&Mrow[wv][0][0])[i] = 0;
+    // bucketing: this lane's (row r2 of pair 0, code a16, b = 0)
+    const uint32_t mrow_l = (uint32_t)(uintptr_t)&Mrow[wv][r2][a16 * W4_NB];
 
     // LDS-DMA: one instruction = 8 rows (plane, v) x 128 B; wave wv sends instructions NI wv .. NI wv + NI - 1 of a slice.  Lane l
     // writes slot l & 7 of row l >> 3 and fetches the slot that belongs there under the XOR
@@ -645,7 +664,9 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
         char* dst = ring + stage * ST + (wv * NI + i) * 1024;
         __builtin_amdgcn_global_load_lds((hg_gptr)(src + doff[i]), (hg_lptr)dst, 16, 0, 0);
     };
-    uint32_t wc[2][4], wn[2][4], bq[8];  // masks of this slice / requested for the next one; the chunk's codes
+    // masks of this slice / requested for the next one; the chunk's codes: bq[p][j] = the codes of row 2 p + r2 in columns
+    // v0 + 8 j + 4 kb .. + 3, the columns of registers 4 j .. 4 j + 3 of a tile
+    uint32_t wc[2][4][2], wn[2][4], bq[4][4];
     // everything but the NI LDS-DMA instructions issued last has landed: the slice before theirs, and the masks / codes requested
     // in front of them
     auto wait_masks = [&]() {
@@ -660,15 +681,24 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int p = 0; p < 4; ++p) wc[ks][p] = wn[ks][p];
+            for (int p = 0; p < 4; ++p) {
+                // the 4-bit pieces of a mask dword, one per byte: even pieces in [0], odd ones in [1] (a piece is then picked with a
+                // byte select inside its multiply: 2 instructions instead of 3).  Opaque, so that hipcc does not narrow the byte
+                // selects back to 4-bit field extracts
+                wc[ks][p][0] = wn[ks][p] & 0x0f0f0f0fu;
+                wc[ks][p][1] = (wn[ks][p] >> 4) & 0x0f0f0f0fu;
+                asm volatile("" : "+v"(wc[ks][p][0]), "+v"(wc[ks][p][1]));
+            }
     };
+#define W4_BQ4(P) "+v"(bq[P][0]), "+v"(bq[P][1]), "+v"(bq[P][2]), "+v"(bq[P][3])
+#define W4_BQ16 W4_BQ4(0), W4_BQ4(1), W4_BQ4(2), W4_BQ4(3)
     auto wait_codes = [&]() {
         if constexpr (NI == 4)
-            asm volatile("s_waitcnt vmcnt(4)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+            asm volatile("s_waitcnt vmcnt(4)" : W4_BQ16 : : "memory");
         else if constexpr (NI == 3)
-            asm volatile("s_waitcnt vmcnt(3)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+            asm volatile("s_waitcnt vmcnt(3)" : W4_BQ16 : : "memory");
         else
-            asm volatile("s_waitcnt vmcnt(2)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bq[4]), "+v"(bq[5]), "+v"(bq[6]), "+v"(bq[7]) : : "memory");
+            asm volatile("s_waitcnt vmcnt(2)" : W4_BQ16 : : "memory");
     };
     // fragment reads: lane l holds column v = l & 31, bytes 16 (l >> 5) .. + 15 of a 32-column half; half h: address ^ (h << 5)
     const uint32_t rd0 = (uint32_t)(uintptr_t)ring + (uint32_t)(i32 * 128 + ((kb ^ ((i32 >> 1) & 7)) << 4));
@@ -687,11 +717,11 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     }
     // code masks in the layout of code_masks_kernel: one dword per 64-column step and row pair, requested one slice ahead
     // (scalar base of the step + 32-bit lane offset: m n < 2^31, accum_w4_supported)
-    uint32_t moff[4], qoff[8];
+    uint32_t moff[4], qoff[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) moff[p] = (uint32_t)((((size_t)mrow[p] * ng * 16 + a16) * 2 + kb) * 4);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) qoff[r] = (uint32_t)((size_t)min(row0 + r, m - 1) * n + i32);
+    for (int p = 0; p < 4; ++p) qoff[p] = (uint32_t)((size_t)mrow[p] * n + 4 * kb);
     auto load_masks = [&](const W4It& it) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -701,12 +731,7 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
         }
     };
 
-    v16i acc[4][NPL];
-    const v4i zero4 = v4i{0, 0, 0, 0};
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int d = 0; d < NPL; ++d) w4_mfma_zero(acc[p][d], zero4);
+    v16i acc[4][NPL];  // born in the first half of a chunk's first slice (w4_mfma_open)
     v4i bf[2][NPL];
 
     // prologue: slices 0 .. 2 in flight, the masks of slice 0; then slice 0 has landed for everybody
@@ -740,7 +765,9 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
             __builtin_amdgcn_s_barrier();
             if (DIAG) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) bq[r] = w4_load_u8(Q + v0, qoff[r]);
+                for (int p = 0; p < 4; ++p)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) bq[p][j] = w4_load_u32(Q + v0 + 8 * j, qoff[p]);
             }
             load_masks(msk);
             w4_next(msk, ns, nchunk);
@@ -750,7 +777,7 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
             // one (measured: expanded in one piece in front of its group, the tile loop was no faster than the first kernel's),
             // and the LDS reads and the LDS-DMA of a half stand behind its first matrix instruction.
             auto piece = [&](int h, int p, int d) {
-                return (int)((((wc[h >> 1][p] >> (16 * (h & 1) + 4 * d)) & 0xfu) * 0x00204081u) & 0x01010101u);
+                return (int)((((wc[h >> 1][p][d & 1] >> (8 * (2 * (h & 1) + (d >> 1)))) & 0xffu) * 0x00204081u) & 0x01010101u);
             };
             v4i af[2];
 #pragma unroll
@@ -781,8 +808,11 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
                     const int nh = p < 3 ? h : h + 1, np = (p + 1) & 3;
 #pragma unroll
                     for (int d = 0; d < NPL; ++d) {
-                        if (d == 0) w4_mfma<true>(acc[p][0], af[g & 1], bf[h & 1][0]);
-                        else w4_mfma<false>(acc[p][d], af[g & 1], bf[h & 1][d]);
+                        if (DIAG && h == 0) {  // masked, never skipped: every tile of the chunk starts here
+                            if (d == 0) w4_mfma_open<true>(acc[p][0], bf[0][0], af[g & 1]);
+                            else w4_mfma_open<false>(acc[p][d], bf[0][d], af[g & 1]);
+                        } else if (d == 0) w4_mfma<true>(acc[p][0], bf[h & 1][0], af[g & 1]);
+                        else w4_mfma<false>(acc[p][d], bf[h & 1][d], af[g & 1]);
                         if (p == 0 && d == 0) feed();
                         if (more && d < NPL - 1) {  // pieces of the next fragment; none behind the group's last instruction
                             constexpr int PER = 4 / (NPL - 1) + (4 % (NPL - 1) != 0);
@@ -813,24 +843,30 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
                 asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]), "+a"(acc[p][2]));
             else asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[p][0]), "+a"(acc[p][1]));
         }
-        const uint32_t mrow0 = (uint32_t)(uintptr_t)&Mrow[wv][0][0];
+        // Register reg of this lane's tile holds column v0 + (reg & 3) + 8 (reg >> 2) + 4 kb, whose code b is byte reg & 3 of
+        // bq[p][reg >> 2].  No branch around the atomic (64 of them per chunk cost more than the additions they saved) and no select
+        // either: a code outside 0 .. 15 takes the bucket that nobody reads
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int i = (reg & 3) + 8 * (reg >> 2) + 4 * kb;  // (row of the pair, code)
-                const int h = i >> 4, a = i & 15;
-                // |digit sum| <= 128 n <= 2^22 (n <= 32768): two digits recombine inside 32 bits.  No branch around the atomic (64 of
-                // them per chunk cost more than the additions they saved): a code outside 0 .. 15 adds zero to bucket b & 15
-                long long val = (long long)(acc[p][0][reg] + (acc[p][1][reg] << 8));
-                if constexpr (NPL == 4) val += (long long)(acc[p][2][reg] + (acc[p][3][reg] << 8)) << 16;
-                if constexpr (NPL == 3) val += (long long)acc[p][2][reg] << 16;
-                const uint32_t b = h ? bq[2 * p + 1] : bq[2 * p];
-                if (b >= 16u) val = 0;
-                w4_lds_add_u64(mrow0 + (uint32_t)((((2 * p + h) * 16 + a) * 16 + (b & 15u)) * 8), (unsigned long long)val);
+                // |digit sum| <= 128 n <= 2^22 (n <= 32768): two digits recombine inside 32 bits, lo = d0 + 256 d1 (and hi = d2 + 256 d3).
+                // The sum lo + 65536 hi without 64-bit arithmetic: t = hi + floor(lo / 65536) (|t| < 2^31), the low word is the low
+                // halves of t and lo side by side, the high word floor(t / 65536)
+                const int lo = acc[p][0][reg] + (acc[p][1][reg] << 8);
+                uint32_t vlo, vhi;
+                if constexpr (NPL == 2) {
+                    vlo = (uint32_t)lo;
+                    vhi = (uint32_t)(lo >> 31);
+                } else {
+                    int t = acc[p][2][reg] + (lo >> 16);
+                    if constexpr (NPL == 4) t += acc[p][3][reg] << 8;
+                    vlo = __builtin_amdgcn_perm((uint32_t)t, (uint32_t)lo, 0x05040100u);
+                    vhi = (uint32_t)(t >> 16);
+                }
+                const uint32_t b = min((bq[p][reg >> 2] >> (8 * (reg & 3))) & 0xffu, 16u);
+                w4_lds_add_u64(mrow_l + (b << 3), p, vlo, vhi);
             }
-#pragma unroll
-            for (int d = 0; d < NPL; ++d) w4_mfma_zero(acc[p][d], zero4);
         }
         { const long long tt = __builtin_amdgcn_s_memtime(); st_flush += tt - st_t0; st_t0 = tt; }
     }
@@ -843,8 +879,10 @@ __device__ __forceinline__ void accum_w4_body(const int8_t* __restrict__ planes_
     for (int r = 0; r < 8; ++r)
         if (row0 + r < m) {
             long long* out = Mpart + ((int64_t)part * m + row0 + r) * 256;
-            for (int i = lane; i < 256; i += 64) out[i] = Mrow[wv][r][i];
+            for (int i = lane; i < 256; i += 64) out[i] = Mrow[wv][r][(i >> 4) * W4_NB + (i & 15)];
         }
+#undef W4_BQ4
+#undef W4_BQ16
 }
 
 // one launch for both words, as onehot_accum_kernel.  The 31-bit word: as many digit planes as top_dense_planes says, one choice for

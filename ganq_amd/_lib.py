@@ -109,6 +109,9 @@ SIGNATURES = {
     "ganq_lut_head_pick": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_float, ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int,
                                           _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "ganq_debug_head_pick_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, ctypes.c_int]),
+    "ganq_lut_head_pick_seeded": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _c_i64, _c_i64,
+                                                 _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "ganq_lut_head_pick_noise": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
     "ganq_debug_lut_plan": (ctypes.c_int, [_c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, ctypes.c_int]),
     "ganq_lut_dequant": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "ganq_lut_embedding": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
@@ -1047,6 +1050,48 @@ def lut_head_pick(x, qweight, lut, bias, bits: int, noise=None, inv_t: float = 1
           _ptr(noise), float(inv_t), code, M, m, n, bits, token.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
           ws.data_ptr(), ws.numel(), _ST)
     return token, out[0], out[1], out[2]
+
+
+def _rng_state(state, who: str):
+    if state.dtype != torch.int64 or tuple(state.shape) != (2,) or not state.is_contiguous():
+        raise GanqHipError(f"{who}: the rng state must be a contiguous int64 [2] tensor {{seed, offset}}, got {state.dtype} {tuple(state.shape)}")
+    return state
+
+
+def lut_head_pick_seeded(x, qweight, lut, bias, bits: int, state, inv_t: float = 1.0, advance: bool = True):
+    """lut_head_pick with the Gumbel noise drawn inside the kernel from `state` (int64 [2] on x's device: seed, offset; Philox4x32-10,
+    include/ganq_hip.h): no [M, out_features] noise exists.  advance: the call's merge launch stores offset + 1 into `state`.
+    -> (token int64, score, lse, logprob fp32), [M] each: the bytes lut_head_pick returns on lut_head_pick_noise(state, M, m)."""
+    code = _act_dtype(x, "x")
+    if lut.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise GanqHipError("x, lut and bias must share one dtype")
+    _rng_state(state, "lut_head_pick_seeded")
+    M, n = x.shape
+    m = lut.shape[0]
+    x, qweight, lut = x.contiguous(), qweight.contiguous(), lut.contiguous()
+    if M > ((1 << 31) - 1) // (2 * max(n, 1)) - 256:  # see lut_linear
+        raise GanqHipError(f"lut_head_pick_seeded: {M} rows of {n} lie beyond the 2 GB window of the kernel's 32-bit offsets and one call "
+                           f"consumes one offset: split the rows over several calls")
+    token = torch.empty(M, dtype=torch.int64, device=x.device)
+    out = torch.empty((3, M), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return token, out[0], out[1], out[2]
+    ws = _workspace(lib().ganq_lut_head_pick_workspace_bytes(M, m, n, bits), x.device)
+    _call("ganq_lut_head_pick_seeded", (x, qweight, lut, bias, state, token, out, ws), x.data_ptr(), qweight.data_ptr(), lut.data_ptr(),
+          _ptr(bias), state.data_ptr(), int(bool(advance)), float(inv_t), code, M, m, n, bits, token.data_ptr(), out[0].data_ptr(),
+          out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(), _ST)
+    return token, out[0], out[1], out[2]
+
+
+def lut_head_pick_noise(state, M: int, m: int, words: bool = False):
+    """the Gumbel noise fp32 [M, m] lut_head_pick_seeded draws from `state` (and with words=True the raw Philox words, as int32 holding
+    the uint32 bits); the state is only read"""
+    _rng_state(state, "lut_head_pick_noise")
+    noise = torch.empty((M, m), dtype=torch.float32, device=state.device)
+    w = torch.empty((M, m), dtype=torch.int32, device=state.device) if words else None
+    if M > 0 and m > 0:
+        _call("ganq_lut_head_pick_noise", (state, noise, w), state.data_ptr(), M, m, noise.data_ptr(), _ptr(w), _ST)
+    return (noise, w) if words else noise
 
 
 def debug_head_pick_plan(M: int, m: int, n: int, bits: int):

@@ -26,6 +26,26 @@
 // rule), eight records in flight at a time, and the 64 lanes merge by exchanges at lane distances 1, 2, ..., 32; lane 0 writes token,
 // score, lse and logprob.
 // No atomics, no memset, no workspace initialisation, no host synchronisation: the same bytes on every call, capturable in a HIP graph.
+//
+// The seeded pick (ganq_lut_head_pick_seeded, the DRAW instantiations of the tile kernel) draws the Gumbel noise in the epilogue
+// instead of reading it: nothing of size [M, m] is drawn, written or read.  The generator is counter-based, Philox4x32-10 (Salmon,
+// Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), one evaluation per lane and 16x16 accumulator tile,
+// whose four words are exactly the four values the lane holds (feature = lane & 15, rows 4 * (lane >> 4) + reg):
+//   key     = (seed_lo, seed_hi)
+//   counter = (o, row >> 2, offset_lo, offset_hi)     o the feature, row the GLOBAL row of x: the noise depends neither on how M
+//                                                     is cut into tile launches nor on RT
+//   word `row & 3` of the result belongs to (row, o)
+//   w -> k = w >> 9 -> u = (2 k + 1) 2^-24            exact in fp32, in [2^-24, 1 - 2^-24]
+//   E = -logf(u), g = -logf(E), z = s + g             the accurate logf both times: E for u near 1 is the upper tail of the Gumbel
+//                                                     distribution, which decides the rare tokens, and a log that is accurate only
+//                                                     absolutely near 1 would distort it
+// g lies in [-2.82, 16.64] and is always finite: no clamp.  The mass of a Gumbel variable above 16.64 (6e-8 per draw) falls on the
+// top value.  Padding features (o >= m) and rows >= M draw nothing; a lane whose four rows are all >= M skips the evaluation (at
+// M = 1 three quarters of the lanes).  Everything after z -- records, tie rule, merge order -- is the code of the noise path.
+// The state {seed, offset} is two uint64 in device memory.  Every tile launch reads it; one call consumes ONE unit of offset
+// whatever its shape: with `advance` set, one lane of the merge launch (stream-ordered after every tile launch of the call) stores
+// offset + 1, so a captured call draws fresh noise on every replay without the host.  ganq_lut_head_pick_noise writes the same
+// noise (and the raw words) as a tensor through the same device functions, for the composition path and the tests.
 #include "common.h"
 
 #include <algorithm>
@@ -70,12 +90,41 @@ __device__ __forceinline__ void pick_merge(PickRec& a, const PickRec& b) {
     a.ob = take ? b.ob : a.ob;
 }
 
-// x, noise and the outputs of rows [r0, r0 + 16 RT) of M; rec4 / reco are [M][feature block]
-template <int BITS, int RT, bool BF16>
+// Philox4x32-10: ten rounds of two 32 x 32 -> 64 bit products, the key bumped by the Weyl constants between rounds
+__device__ __forceinline__ p_u32x4 pick_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return p_u32x4{c0, c1, c2, c3};
+}
+
+// the four words of feature o and rows 4 rg .. 4 rg + 3 under the state (seed, offset)
+__device__ __forceinline__ p_u32x4 pick_draw_words(uint64_t seed, uint64_t offset, int o, int rg) {
+    return pick_philox((uint32_t)o, (uint32_t)rg, (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// word -> Gumbel noise: u = (2 (w >> 9) + 1) 2^-24 is exact (an odd 24-bit integer, then a power of two)
+__device__ __forceinline__ float pick_gumbel(uint32_t w) {
+    const float u = (float)(2u * (w >> 9) + 1u) * 0x1p-24f;
+    return -logf(-logf(u));
+}
+
+// x, noise and the outputs of rows [r0, r0 + 16 RT) of M; rec4 / reco are [M][feature block].  aux: the noise (fp32 [M][m], or NULL),
+// DRAW: the state {seed, offset} the noise is drawn from instead
+template <int BITS, int RT, bool BF16, bool DRAW>
 __global__ __launch_bounds__(PW * 64) void lut_head_pick_tile_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ qw,
                                                                     const uint16_t* __restrict__ lut, const uint16_t* __restrict__ bias,
-                                                                    const float* __restrict__ noise, float inv_t, int r0, int M, int m, int n,
+                                                                    const void* __restrict__ aux, float inv_t, int r0, int M, int m, int n,
                                                                     float4* __restrict__ rec4, int* __restrict__ reco) {
+    const float* __restrict__ noise = DRAW ? nullptr : static_cast<const float*>(aux);
     constexpr int V = 1 << BITS;
     constexpr int KC = RT <= 2 ? 4 : 2;              // groups in flight per wave (loads issued one chunk ahead); fewer with many row tiles,
                                                      // whose activations would otherwise leave one wave per SIMD
@@ -202,9 +251,25 @@ __global__ __launch_bounds__(PW * 64) void lut_head_pick_tile_kernel(const uint1
         bv[t] = 0.f;
         if (bias && ok[t]) bv[t] = BF16 ? __builtin_bit_cast(float, (uint32_t)bias[o] << 16) : (float)__builtin_bit_cast(_Float16, bias[o]);
     }
+    uint64_t seed = 0, offset = 0;
+    if constexpr (DRAW) {
+        seed = static_cast<const uint64_t*>(aux)[0];
+        offset = static_cast<const uint64_t*>(aux)[1];
+    }
     PickRec mine[RT];  // after the reductions lane (q, col) keeps the record of row 16 r + 4 q + (col & 3)
 #pragma unroll
-    for (int r = 0; r < RT; ++r)
+    for (int r = 0; r < RT; ++r) {
+        p_f32x4 gn[2] = {p_f32x4{0.f, 0.f, 0.f, 0.f}, p_f32x4{0.f, 0.f, 0.f, 0.f}};
+        if constexpr (DRAW) {  // one evaluation per tile: its word i is the lane's row i (r0 is a multiple of 64)
+            const int rb = r0 + 16 * r + 4 * q;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+                if (ok[t] && rb < M) {
+                    const p_u32x4 w = pick_draw_words(seed, offset, o0 + 16 * t + col, rb >> 2);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) gn[t][i] = pick_gumbel(w[i]);
+                }
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = r0 + 16 * r + 4 * q + i;
@@ -214,7 +279,11 @@ __global__ __launch_bounds__(PW * 64) void lut_head_pick_tile_kernel(const uint1
                 const int o = o0 + 16 * t + col;
                 const float s = (acc[t][r][i] + bv[t]) * inv_t;
                 float z = s;
-                if (noise && ok[t] && row < M) z += noise[(int64_t)row * m + o];
+                if constexpr (DRAW) {
+                    if (ok[t] && row < M) z += gn[t][i];
+                } else {
+                    if (noise && ok[t] && row < M) z += noise[(int64_t)row * m + o];
+                }
                 rt[t].mx = ok[t] ? s : PICK_NEG;
                 rt[t].sm = ok[t] ? 1.f : 0.f;
                 rt[t].zb = ok[t] ? z : -INFINITY;
@@ -234,6 +303,7 @@ __global__ __launch_bounds__(PW * 64) void lut_head_pick_tile_kernel(const uint1
             pick_merge(rt[0], rt[1]);  // the wave's two tiles
             if ((col & 3) == i) mine[r] = rt[0];
         }
+    }
     // across the four waves: waves 1..3 leave their records in LDS, wave 0 merges them in wave order and writes
     if (wv > 0 && col < 4) {
 #pragma unroll
@@ -266,9 +336,9 @@ __global__ __launch_bounds__(PW * 64) void lut_head_pick_tile_kernel(const uint1
     }
 }
 
-__global__ __launch_bounds__(PCW * 64) void lut_head_pick_merge_kernel(const float4* __restrict__ rec4, const int* __restrict__ reco, int M,
-                                                                     int blocks, int64_t* __restrict__ token, float* __restrict__ score,
-                                                                     float* __restrict__ lse, float* __restrict__ logprob) {
+__device__ __forceinline__ void pick_merge_rows(const float4* __restrict__ rec4, const int* __restrict__ reco, int M, int blocks,
+                                                int64_t* __restrict__ token, float* __restrict__ score, float* __restrict__ lse,
+                                                float* __restrict__ logprob) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * PCW + (threadIdx.x >> 6);  // one wave per row (no barrier below: a wave may leave)
     if (row >= M) return;
@@ -324,28 +394,70 @@ __global__ __launch_bounds__(PCW * 64) void lut_head_pick_merge_kernel(const flo
     logprob[row] = sb - l;
 }
 
+__global__ __launch_bounds__(PCW * 64) void lut_head_pick_merge_kernel(const float4* __restrict__ rec4, const int* __restrict__ reco, int M,
+                                                                     int blocks, int64_t* __restrict__ token, float* __restrict__ score,
+                                                                     float* __restrict__ lse, float* __restrict__ logprob) {
+    pick_merge_rows(rec4, reco, M, blocks, token, score, lse, logprob);
+}
+
+// the merge launch of a seeded call that advances its state: every tile launch of the call has read the state by now (stream order),
+// so one lane stores offset + 1 (an ordinary 64-bit vector store)
+__global__ __launch_bounds__(PCW * 64) void lut_head_pick_merge_advance_kernel(const float4* __restrict__ rec4, const int* __restrict__ reco,
+                                                                             int M, int blocks, int64_t* __restrict__ token,
+                                                                             float* __restrict__ score, float* __restrict__ lse,
+                                                                             float* __restrict__ logprob, uint64_t* rng) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) rng[1] = rng[1] + 1;
+    pick_merge_rows(rec4, reco, M, blocks, token, score, lse, logprob);
+}
+
+// noise [M][m] (and the raw words) of the state, through the device functions of the tile kernel: a thread per (four rows, feature)
+__global__ __launch_bounds__(256) void lut_head_pick_noise_kernel(const uint64_t* __restrict__ rng, int M, int m, float* __restrict__ noise,
+                                                                 uint32_t* __restrict__ words) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)((M + 3) >> 2) * m) return;
+    const int rg = (int)(idx / m), o = (int)(idx - (int64_t)rg * m);
+    const p_u32x4 w = pick_draw_words(rng[0], rng[1], o, rg);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = 4 * rg + i;
+        if (row < M) {
+            noise[(int64_t)row * m + o] = pick_gumbel(w[i]);
+            if (words) words[(int64_t)row * m + o] = w[i];
+        }
+    }
+}
+
 static int64_t head_pick_blocks(int64_t m) { return (m + PFB - 1) / PFB; }
 static int head_pick_rt(int64_t rows) { return rows <= 16 ? 1 : (rows <= 32 ? 2 : (rows <= 48 ? 3 : 4)); }
 
-template <int BITS, int RT>
-static void launch_head_pick_rt(const uint16_t* x, const uint32_t* qw, const uint16_t* lut, const uint16_t* bias, const float* noise,
+// aux: the noise (or NULL), or with DRAW the state
+template <int BITS, int RT, bool DRAW>
+static void launch_head_pick_rt(const uint16_t* x, const uint32_t* qw, const uint16_t* lut, const uint16_t* bias, const void* aux,
                                 float inv_t, int dtype, int r0, int M, int m, int n, float4* rec4, int* reco, hipStream_t stream) {
     const dim3 grid((unsigned)head_pick_blocks(m));
     if (dtype == 1)
-        hipLaunchKernelGGL((lut_head_pick_tile_kernel<BITS, RT, true>), grid, dim3(PW * 64), 0, stream, x, qw, lut, bias, noise, inv_t, r0, M, m,
-                           n, rec4, reco);
+        hipLaunchKernelGGL((lut_head_pick_tile_kernel<BITS, RT, true, DRAW>), grid, dim3(PW * 64), 0, stream, x, qw, lut, bias, aux, inv_t, r0, M,
+                           m, n, rec4, reco);
     else
-        hipLaunchKernelGGL((lut_head_pick_tile_kernel<BITS, RT, false>), grid, dim3(PW * 64), 0, stream, x, qw, lut, bias, noise, inv_t, r0, M, m,
-                           n, rec4, reco);
+        hipLaunchKernelGGL((lut_head_pick_tile_kernel<BITS, RT, false, DRAW>), grid, dim3(PW * 64), 0, stream, x, qw, lut, bias, aux, inv_t, r0, M,
+                           m, n, rec4, reco);
 }
 
-template <int BITS>
-static void launch_head_pick_bits(int rt, const uint16_t* x, const uint32_t* qw, const uint16_t* lut, const uint16_t* bias, const float* noise,
+template <int BITS, bool DRAW>
+static void launch_head_pick_bits(int rt, const uint16_t* x, const uint32_t* qw, const uint16_t* lut, const uint16_t* bias, const void* aux,
                                   float inv_t, int dtype, int r0, int M, int m, int n, float4* rec4, int* reco, hipStream_t stream) {
-    if (rt == 1) launch_head_pick_rt<BITS, 1>(x, qw, lut, bias, noise, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
-    else if (rt == 2) launch_head_pick_rt<BITS, 2>(x, qw, lut, bias, noise, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
-    else if (rt == 3) launch_head_pick_rt<BITS, 3>(x, qw, lut, bias, noise, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
-    else launch_head_pick_rt<BITS, 4>(x, qw, lut, bias, noise, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    if (rt == 1) launch_head_pick_rt<BITS, 1, DRAW>(x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    else if (rt == 2) launch_head_pick_rt<BITS, 2, DRAW>(x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    else if (rt == 3) launch_head_pick_rt<BITS, 3, DRAW>(x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    else launch_head_pick_rt<BITS, 4, DRAW>(x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+}
+
+template <bool DRAW>
+static void launch_head_pick(int bits, int rt, const uint16_t* x, const uint32_t* qw, const uint16_t* lut, const uint16_t* bias, const void* aux,
+                             float inv_t, int dtype, int r0, int M, int m, int n, float4* rec4, int* reco, hipStream_t stream) {
+    if (bits == 2) launch_head_pick_bits<2, DRAW>(rt, x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    else if (bits == 3) launch_head_pick_bits<3, DRAW>(rt, x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
+    else launch_head_pick_bits<4, DRAW>(rt, x, qw, lut, bias, aux, inv_t, dtype, r0, M, m, n, rec4, reco, stream);
 }
 
 }  // namespace ganq
@@ -374,10 +486,10 @@ extern "C" int ganq_debug_head_pick_plan(int64_t M, int64_t m, int64_t n, int bi
     return 0;
 }
 
-extern "C" int ganq_lut_head_pick(const void* x, const int32_t* qweight, const void* lut, const void* bias, const float* noise, float inv_t,
-                                  int dtype, int64_t M, int64_t m, int64_t n, int bits, int64_t* token, float* score, float* lse,
-                                  float* logprob, void* workspace, size_t workspace_bytes, void* stream_) {
-    const char* who = "ganq_lut_head_pick";
+// both entries: noise (or NULL) for ganq_lut_head_pick; rng_state, drawn from in the epilogue, for ganq_lut_head_pick_seeded
+static int head_pick_run(const char* who, const void* x, const int32_t* qweight, const void* lut, const void* bias, const float* noise,
+                         uint64_t* rng_state, bool seeded, int advance, float inv_t, int dtype, int64_t M, int64_t m, int64_t n, int bits,
+                         int64_t* token, float* score, float* lse, float* logprob, void* workspace, size_t workspace_bytes, void* stream_) {
     if (M < 0 || m < 0 || n < 0) return fail(-1, "%s: negative shape", who);
     if (M == 0) return 0;
     if (dtype != 0 && dtype != 1) return fail(-2, "%s: dtype %d (0 = fp16, 1 = bf16)", who, dtype);
@@ -387,6 +499,8 @@ extern "C" int ganq_lut_head_pick(const void* x, const int32_t* qweight, const v
     if (!std::isfinite(inv_t) || !(inv_t > 0.f)) return fail(-2, "%s: inv_t=%g must be finite and positive", who, (double)inv_t);
     if (m > INT32_MAX / 2 || n > INT32_MAX / 2 || M > INT32_MAX / 2) return fail(-1, "%s: shape too large", who);
     if (!x || !qweight || !lut || !token || !score || !lse || !logprob) return fail(-3, "%s: null pointer", who);
+    if (seeded && !rng_state) return fail(-3, "%s: null rng_state", who);
+    if (seeded && (reinterpret_cast<uintptr_t>(rng_state) & 7) != 0) return fail(-2, "%s: rng_state must be 8-byte aligned", who);
     if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return fail(-2, "%s: x must be 16-byte aligned", who);
     if ((reinterpret_cast<uintptr_t>(lut) & 3) != 0) return fail(-2, "%s: lut must be 4-byte aligned", who);
     const size_t need = ganq_lut_head_pick_workspace_bytes(M, m, n, bits);
@@ -406,13 +520,46 @@ extern "C" int ganq_lut_head_pick(const void* x, const int32_t* qweight, const v
     const uint16_t* bp = static_cast<const uint16_t*>(bias);
     for (int64_t r0 = 0; r0 < M; r0 += PROWS) {  // one tile launch per 64 rows
         const int rt = head_pick_rt(std::min<int64_t>(PROWS, M - r0));
-        if (bits == 2) launch_head_pick_bits<2>(rt, xp, qw, lp, bp, noise, inv_t, dtype, (int)r0, (int)M, (int)m, (int)n, rec4, reco, stream);
-        else if (bits == 3) launch_head_pick_bits<3>(rt, xp, qw, lp, bp, noise, inv_t, dtype, (int)r0, (int)M, (int)m, (int)n, rec4, reco, stream);
-        else launch_head_pick_bits<4>(rt, xp, qw, lp, bp, noise, inv_t, dtype, (int)r0, (int)M, (int)m, (int)n, rec4, reco, stream);
+        if (seeded) launch_head_pick<true>(bits, rt, xp, qw, lp, bp, rng_state, inv_t, dtype, (int)r0, (int)M, (int)m, (int)n, rec4, reco, stream);
+        else launch_head_pick<false>(bits, rt, xp, qw, lp, bp, noise, inv_t, dtype, (int)r0, (int)M, (int)m, (int)n, rec4, reco, stream);
         GANQ_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(lut_head_pick_merge_kernel, dim3((unsigned)((M + PCW - 1) / PCW)), dim3(PCW * 64), 0, stream, rec4, reco, (int)M, (int)blocks,
-                       token, score, lse, logprob);
+    const dim3 grid((unsigned)((M + PCW - 1) / PCW));
+    if (seeded && advance)
+        hipLaunchKernelGGL(lut_head_pick_merge_advance_kernel, grid, dim3(PCW * 64), 0, stream, rec4, reco, (int)M, (int)blocks, token, score, lse,
+                           logprob, rng_state);
+    else
+        hipLaunchKernelGGL(lut_head_pick_merge_kernel, grid, dim3(PCW * 64), 0, stream, rec4, reco, (int)M, (int)blocks, token, score, lse,
+                           logprob);
+    GANQ_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ganq_lut_head_pick(const void* x, const int32_t* qweight, const void* lut, const void* bias, const float* noise, float inv_t,
+                                  int dtype, int64_t M, int64_t m, int64_t n, int bits, int64_t* token, float* score, float* lse,
+                                  float* logprob, void* workspace, size_t workspace_bytes, void* stream_) {
+    return head_pick_run("ganq_lut_head_pick", x, qweight, lut, bias, noise, nullptr, false, 0, inv_t, dtype, M, m, n, bits, token, score, lse,
+                         logprob, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ganq_lut_head_pick_seeded(const void* x, const int32_t* qweight, const void* lut, const void* bias, uint64_t* rng_state,
+                                         int advance, float inv_t, int dtype, int64_t M, int64_t m, int64_t n, int bits, int64_t* token,
+                                         float* score, float* lse, float* logprob, void* workspace, size_t workspace_bytes, void* stream_) {
+    return head_pick_run("ganq_lut_head_pick_seeded", x, qweight, lut, bias, nullptr, rng_state, true, advance, inv_t, dtype, M, m, n, bits,
+                         token, score, lse, logprob, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int ganq_lut_head_pick_noise(const uint64_t* rng_state, int64_t M, int64_t m, float* noise, uint32_t* words, void* stream_) {
+    const char* who = "ganq_lut_head_pick_noise";
+    if (M < 0 || m < 0) return fail(-1, "%s: negative shape", who);
+    if (M == 0 || m == 0) return 0;
+    if (m > INT32_MAX / 2 || M > INT32_MAX / 2) return fail(-1, "%s: shape too large", who);
+    if (!rng_state || !noise) return fail(-3, "%s: null pointer", who);
+    if ((reinterpret_cast<uintptr_t>(rng_state) & 7) != 0) return fail(-2, "%s: rng_state must be 8-byte aligned", who);
+    const int64_t grid = (((M + 3) >> 2) * m + 255) / 256;
+    if (grid > INT32_MAX) return fail(-1, "%s: %lld x %lld beyond one launch: split the rows", who, (long long)M, (long long)m);
+    hipLaunchKernelGGL(lut_head_pick_noise_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream_), rng_state, (int)M,
+                       (int)m, noise, words);
     GANQ_LAUNCH_CHECK();
     return 0;
 }

@@ -420,10 +420,11 @@ def causal_lm_nll(model: nn.Module, input_ids: torch.Tensor, labels: Optional[to
     return head.nll(hidden[:, :-1, :], labels[:, 1:].to(hidden.device))
 
 
-def causal_lm_next_token(model: nn.Module, input_ids: torch.Tensor, temperature: float = 0.0, generator=None, **base_model_kwargs):
+def causal_lm_next_token(model: nn.Module, input_ids: torch.Tensor, temperature: float = 0.0, generator=None, rng=None, **base_model_kwargs):
     """The next token of a causal LM whose output head is a packed GanqHipQuantLinear, without the [batch, vocab] logits:
     `model.base_model(input_ids, **base_model_kwargs)` runs and the hidden state of the last position goes through `head.pick`
-    (greedy at temperature 0, a sample from softmax(logits / temperature) drawn with `generator` otherwise).
+    (greedy at temperature 0, a sample from softmax(logits / temperature) drawn with `generator` otherwise -- or, with
+    rng=PickRng(seed), inside the head's kernel from that state, which the call advances by one: no [batch, vocab] noise either).
     -> (token int64 [batch], logprob fp32 [batch], the base model's outputs -- so a caller can carry `past_key_values`).  No graph is
     built; the gradient of logprob is taken in the training pass, through `causal_lm_nll`.
     Raises for a head that is not packed and for a config that scales or caps the logits after the head."""
@@ -439,7 +440,7 @@ def causal_lm_next_token(model: nn.Module, input_ids: torch.Tensor, temperature:
                                       f"the token straight from the head would miss it")
     with torch.no_grad():
         outputs = model.base_model(input_ids, **base_model_kwargs)
-        token, logprob = head.pick(outputs[0][:, -1, :], temperature=temperature, generator=generator)
+        token, logprob = head.pick(outputs[0][:, -1, :], temperature=temperature, generator=generator, rng=rng)
     return token, logprob, outputs
 
 

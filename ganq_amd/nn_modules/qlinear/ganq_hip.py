@@ -48,6 +48,45 @@ GEMV_MAX_ROWS = 64
 NLL_CHUNK_BYTES = 256 << 20  # logits (and their fp32 copy) a chunk of GanqHipQuantLinear.nll's chunked path may form; tests lower it
 
 
+class PickRng:
+    """The state of the counter-based generator `GanqHipQuantLinear.pick(..., rng=)` draws its Gumbel noise from inside the kernel
+    (Philox4x32-10, csrc/lut_head_pick.hip): an int64 [2] device tensor {seed, offset}, both read as unsigned 64-bit.  A pick is a
+    pure function of (inputs, seed, offset) and consumes one unit of offset whatever its shape; the kernel itself advances the
+    offset, so a pick captured in a HIP graph samples afresh on every replay.
+      .state          the tensor (the kernels read and advance it in place)
+      .seed .offset   read it back (a device synchronisation)
+    copy / deepcopy give a generator with a tensor of its own at the same state; pickling stores the two integers (and the device)."""
+    _MASK = (1 << 64) - 1
+
+    def __init__(self, seed: int, offset: int = 0, device=None):
+        seed, offset = int(seed), int(offset)
+        if not (0 <= seed <= self._MASK and 0 <= offset <= self._MASK):
+            raise ValueError(f"PickRng: seed and offset must lie in [0, 2^64), got {seed}, {offset}")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"PickRng: the state lives on the GPU, got device {device}")
+        signed = [v - (1 << 64) if v >= (1 << 63) else v for v in (seed, offset)]
+        self.state = torch.tensor(signed, dtype=torch.int64, device=device)
+
+    @property
+    def seed(self) -> int:
+        return int(self.state[0].item()) & self._MASK
+
+    @property
+    def offset(self) -> int:
+        return int(self.state[1].item()) & self._MASK
+
+    @property
+    def device(self):
+        return self.state.device
+
+    def __reduce__(self):
+        return (PickRng, (self.seed, self.offset, str(self.state.device)))
+
+    def __repr__(self):
+        return f"PickRng(seed={self.seed}, offset={self.offset}, device='{self.state.device}')"
+
+
 class GanqHipQuantLinear(BaseQuantLinear):
     SUPPORTS_BITS = [2, 3, 4]
     SUPPORTS_GROUP_SIZE = [-1, 16, 32, 64, 128]  # accepted and ignored, as GANQ ignores it (ganq.py:489-495)
@@ -344,13 +383,18 @@ class GanqHipQuantLinear(BaseQuantLinear):
 
     # ---- the next token of the layer as an output head, without the full logits
     @torch.no_grad()
-    def pick(self, x: torch.Tensor, temperature: float = 0.0, generator=None, noise: torch.Tensor = None, fused=None):
+    def pick(self, x: torch.Tensor, temperature: float = 0.0, generator=None, noise: torch.Tensor = None, fused=None, rng: PickRng = None):
         """The next token of the layer as an output head: x [..., in_features] -> (token int64, logprob fp32) of shape x.shape[:-1].
           temperature == 0: greedy, token = argmax of the logits (the smallest index among equals in the fused path), logprob its
             plain log-softmax value;
           temperature > 0: a token sampled from softmax(logits / temperature) by the Gumbel-max rule, token = argmax of
             logits / temperature + noise, logprob = log_softmax(logits / temperature)[token].  noise: fp32 [..., out_features]; by
             default -log(E) with E = torch.empty(M, out_features).exponential_(generator=generator), clamped away from 0.
+          rng (a PickRng on x's device, instead of generator / noise): the noise is a function of (rng.seed, rng.offset, row,
+            feature) and the call advances rng.offset by one, on the device.  In the fused path the kernel draws it in its epilogue
+            -- no [M, out_features] tensor exists and the call can be captured in a HIP graph, every replay a fresh sample; the
+            composition fills a buffer with the same noise (`_lib.lut_head_pick_noise`) and advances the state with one torch op.
+            temperature == 0 ignores rng and leaves it untouched.
           fused (the default of a layer with neither outliers nor an adapter; True on any other layer raises): one library call
             (csrc/lut_head_pick.hip) reduces the unrounded fp32 logits tile by tile, the same logits `nll` uses: at temperature 1
             logprob and -nll(x, token) are the same number up to the order of the sums;
@@ -369,9 +413,17 @@ class GanqHipQuantLinear(BaseQuantLinear):
         elif fused and not can_fuse:
             raise ValueError("GanqHipQuantLinear.pick: fused=True serves a layer with neither outliers nor an adapter; this layer takes "
                              "the composition (fused=False or None)")
+        if rng is not None:
+            if not isinstance(rng, PickRng):
+                raise TypeError(f"GanqHipQuantLinear.pick: rng must be a PickRng, got {type(rng).__name__}")
+            if generator is not None or noise is not None:
+                raise ValueError("GanqHipQuantLinear.pick: rng draws the noise itself; pass it without generator and noise")
+            if rng.state.device != x.device:
+                raise ValueError(f"GanqHipQuantLinear.pick: the rng state lives on {rng.state.device}, x on {x.device}")
         shape = tuple(x.shape[:-1])
         x2 = x.detach().reshape(-1, self.in_features)
         M, m = x2.shape[0], self.out_features
+        seeded = rng is not None and temperature > 0 and M > 0
         if noise is not None:
             if noise.dtype != torch.float32:
                 raise TypeError(f"GanqHipQuantLinear.pick: noise must be float32, got {noise.dtype}")
@@ -381,7 +433,10 @@ class GanqHipQuantLinear(BaseQuantLinear):
         inv_t = 1.0
         if temperature > 0:
             inv_t = 1.0 / temperature
-            if noise is None:
+            if seeded:
+                if not fused:
+                    noise = _lib.lut_head_pick_noise(rng.state, M, m)
+            elif noise is None:
                 e = torch.empty(M, m, dtype=torch.float32, device=x.device).exponential_(generator=generator)
                 noise = e.clamp_min_(torch.finfo(torch.float32).tiny).log_().neg_()
         if fused:
@@ -389,7 +444,10 @@ class GanqHipQuantLinear(BaseQuantLinear):
             if lut.dtype != x2.dtype:
                 lut = lut.to(x2.dtype)
                 bias = None if bias is None else bias.to(x2.dtype)
-            token, _, _, logprob = _lib.lut_head_pick(x2, self.qweight, lut, bias, self.bits, noise, inv_t)
+            if seeded:
+                token, _, _, logprob = _lib.lut_head_pick_seeded(x2, self.qweight, lut, bias, self.bits, rng.state, inv_t, advance=True)
+            else:
+                token, _, _, logprob = _lib.lut_head_pick(x2, self.qweight, lut, bias, self.bits, noise, inv_t)
             return token.reshape(shape), logprob.reshape(shape)
         token = torch.empty(M, dtype=torch.int64, device=x2.device)
         logprob = torch.empty(M, dtype=torch.float32, device=x2.device)
@@ -399,6 +457,8 @@ class GanqHipQuantLinear(BaseQuantLinear):
             t = torch.argmax(s if noise is None else s + noise[r:r + step], dim=-1)
             token[r:r + step] = t
             logprob[r:r + step] = s.gather(1, t.unsqueeze(1)).squeeze(1) - torch.logsumexp(s, dim=-1)
+        if seeded:
+            rng.state[1:].add_(1)  # one call, one unit of offset (two's complement: the unsigned sum)
         return token.reshape(shape), logprob.reshape(shape)
 
 

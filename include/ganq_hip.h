@@ -419,6 +419,27 @@ int ganq_lut_head_pick(const void* x, const int32_t* qweight, const void* lut, c
                        void* workspace, size_t workspace_bytes, void* stream);
 int ganq_debug_head_pick_plan(int64_t M, int64_t m, int64_t n, int bits, int* out, int out_len);
 
+/* ---- the sampled pick with the noise drawn inside the kernel (csrc/lut_head_pick.hip).  ganq_lut_head_pick_seeded is
+ * ganq_lut_head_pick with noise[r][o] = g(r, o) computed in the epilogue of the tile kernel instead of read: nothing of size [M, m]
+ * is drawn, written or read, and the call is a pure function of (inputs, seed, offset).
+ *   rng_state  device memory, 8-byte aligned: { uint64 seed, uint64 offset }
+ *   g(r, o)    Philox4x32-10 with key (seed_lo, seed_hi) and counter (o, r >> 2, offset_lo, offset_hi); of its four words the
+ *              word w = out[r & 3] belongs to (r, o); u = (2 (w >> 9) + 1) 2^-24 (exact in fp32, in [2^-24, 1 - 2^-24]),
+ *              g = -logf(-logf(u)) in [-2.82, 16.64]: always finite; the mass of a Gumbel variable above 16.64 (6e-8 per draw)
+ *              falls on the top value.  r is the row of x within the call, whatever the launches the call is cut into.
+ *   advance    one call consumes ONE unit of offset whatever its shape.  Non-zero: one lane of the merge launch, which is
+ *              stream-ordered after every tile launch of the call, stores offset + 1 (64-bit), so the next call -- or the next
+ *              replay of a captured call -- draws fresh noise without the host.  Zero: the 16 bytes are only read.
+ * Same workspace and sizer, same outputs, tie rule and error codes as ganq_lut_head_pick, and -3 for a null, -2 for a misaligned
+ * rng_state.  No atomics, no memset, no host synchronisation; M == 0 is a no-op that leaves the state.
+ * ganq_lut_head_pick_noise writes noise[M][m] = g(r, o) of the state (fp32) and, if words is not NULL, the raw Philox word of
+ * every element (uint32 [M][m]) through the same device functions; it never advances the state.  ganq_lut_head_pick on that
+ * noise returns the bytes ganq_lut_head_pick_seeded returns. */
+int ganq_lut_head_pick_seeded(const void* x, const int32_t* qweight, const void* lut, const void* bias, uint64_t* rng_state, int advance,
+                              float inv_t, int dtype, int64_t M, int64_t m, int64_t n, int bits, int64_t* token, float* score, float* lse,
+                              float* logprob, void* workspace, size_t workspace_bytes, void* stream);
+int ganq_lut_head_pick_noise(const uint64_t* rng_state, int64_t M, int64_t m, float* noise, uint32_t* words, void* stream);
+
 /* ---- a9 backward -- the gradients autograd takes through FakeQuantLinear.forward (fake.py:88-89).  Same qweight / lut layout,
  * dtypes and shapes as ganq_lut_linear_fwd (any M >= 1, any m >= 1, n a multiple of 32; dtype 0 = fp16, 1 = bf16 for dy, x, lut, dx):
  *   bwd_input: dx [M,n] = dy [M,m] @ dequant(qweight, lut) (+ addend [M,n] fp32, or NULL); fp32 accumulation over all of m,
